@@ -4,7 +4,7 @@ BASELINE.json metric: "TPC-H SF100 total query time (s) + rows/sec scan,
 1/2/4/8 MI355X", on synthetic TPC-H-shaped Parquet data. One step = one run
 of the full 22-query suite.
 
-Data path (default ``--source parquet``):
+Data path of a ``--full`` run (``--source parquet``, its default):
   1. each rank generates its hash partition of the SF tables on the GPU
      (spec distributions, models/tpch/datagen.py) and writes it as snappy
      Parquet files with a parallel writer (models/tpch/parquet_gen.py); a
@@ -31,6 +31,24 @@ against the CPU engine over the same files (``cpu_check``).
 ``scan_rows_per_s`` counts base-table rows the queries actually read (each
 table once per query; index / range searches count only the rows touched).
 ``--source hbm`` runs on tables generated straight into HBM (no Parquet).
+
+A plain run (no ``--full``) does only what the headline figure needs: it
+generates the tables straight into HBM (``--source`` defaults to ``hbm``),
+runs the first (cold) suite that builds the derived structures, the
+``--warmup`` suites and the ``--steps`` timed suites, and prints the result
+line. ``--full`` adds everything else, as described above: the Parquet data
+path (``--source`` defaults to ``parquet``: dataset write, cold file read +
+GPU decode), the eager and ad-hoc suites (``--eager-steps``,
+``--vary-params``), the digest verification of every timed result against the
+cold run and the CPU-engine check at ``--sf <= 1``.
+
+``--dump-outputs DIR`` writes what the last timed step returned to the caller
+(one Arrow table per query) as ``DIR/q<NN>.<II>_<column>.npy`` in float64
+(integers, dates, decimals and booleans as their float64 value; strings as the
+float64 value of a CRC-32 of their UTF-8 bytes; NULL as NaN), with the column
+order in ``DIR/manifest.json``. The generated data and the validation
+parameters are fixed, so two builds run with the same arguments dump the same
+arrays.
 
 Single GPU:  python bench.py --gpus 1 --steps 3 --warmup 1
 N GPUs:      python bench.py --gpus N ...   (launches N rank processes itself), or
@@ -65,6 +83,70 @@ def parse_queries(s: str):
         elif part:
             out.append(int(part))
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _as_float_array(col):
+    """One result column as a float64 numpy array: numbers, decimals, dates
+    and booleans by value, strings by the CRC-32 of their UTF-8 bytes, NULL as
+    NaN."""
+    import zlib
+    import numpy as np
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    arr = col.combine_chunks() if isinstance(col, pa.ChunkedArray) else col
+    t = arr.type
+    if pa.types.is_dictionary(t):
+        arr = arr.cast(t.value_type)
+        t = arr.type
+    if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_binary(t) or pa.types.is_large_binary(t):
+        vals = [float("nan") if v is None else float(zlib.crc32(v if isinstance(v, bytes) else v.encode()))
+                for v in arr.to_pylist()]
+        return np.asarray(vals, dtype=np.float64)
+    if pa.types.is_date32(t):
+        arr = arr.cast(pa.int32())
+    elif pa.types.is_date64(t) or pa.types.is_timestamp(t) or pa.types.is_time(t) or pa.types.is_duration(t):
+        arr = arr.cast(pa.int64())
+    elif pa.types.is_boolean(t):
+        arr = arr.cast(pa.int8())
+    elif not (pa.types.is_integer(t) or pa.types.is_floating(t) or pa.types.is_decimal(t)):
+        # nested / other types: by the CRC-32 of their printed value
+        vals = [float("nan") if v is None else float(zlib.crc32(repr(v).encode())) for v in arr.to_pylist()]
+        return np.asarray(vals, dtype=np.float64)
+    out = pc.cast(arr, pa.float64(), safe=False)
+    return np.asarray(out.to_numpy(zero_copy_only=False), dtype=np.float64)
+
+
+def dump_outputs(out_dir: str, results: dict) -> None:
+    """Write one timed step's results (query number -> Arrow table) as
+    ``q<NN>.<II>_<column>.npy`` float64 arrays plus ``manifest.json``. Results past
+    DUMP_BUDGET_BYTES in all are cut to a fixed, seeded sample of their rows
+    (the same rows for the same result sizes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(8 * t.num_rows * t.num_columns for t in results.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    manifest = {}
+    for q in sorted(results):
+        t = results[q]
+        rows = None
+        if keep < 1.0 and t.num_rows > 1:
+            n = max(1, int(t.num_rows * keep))
+            rows = np.sort(np.random.default_rng(1234 + q).choice(t.num_rows, size=n, replace=False))
+        cols = []
+        for i, name in enumerate(t.column_names):
+            v = _as_float_array(t.column(i))
+            if rows is not None:
+                v = v[rows]
+            fname = f"q{q:02d}.{i:02d}_{''.join(c if c.isalnum() else '_' for c in name)}"
+            np.save(os.path.join(out_dir, fname + ".npy"), v)
+            cols.append({"name": name, "file": fname + ".npy", "type": str(t.schema.field(i).type)})
+        manifest[f"q{q:02d}"] = {"rows": t.num_rows, "rows_written": t.num_rows if rows is None else len(rows),
+                                 "columns": cols}
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
 
 
 _MODE_TAG = {"recorded": "R", "replayed": "P", "graph": "G", "partial": "x"}
@@ -109,7 +191,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--sf", type=float, default=100.0)
     ap.add_argument("--queries", default="1-22")
-    ap.add_argument("--source", choices=["parquet", "hbm"], default="parquet")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the Parquet data path (cold read + GPU "
+                         "decode), the eager and ad-hoc suites, digest verification, the CPU check at sf <= 1")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's query results to DIR as float64 .npy arrays")
+    ap.add_argument("--source", choices=["parquet", "hbm"], default=None,
+                    help="where the tables come from (default: parquet with --full, else hbm)")
     ap.add_argument("--data-dir", default=os.environ.get("IGLOO_BENCH_DIR", "/tmp/igloo_tpch"))
     ap.add_argument("--lean", action="store_true", help="skip comment columns no query reads")
     ap.add_argument("--parquet-codec", choices=["snappy", "zstd", "none"], default="snappy",
@@ -120,14 +208,20 @@ def main():
     ap.add_argument("--digests-out", default="", help="write the cold run's result digests (JSON) here")
     ap.add_argument("--cpu", action="store_true", help="run on CPU (debug)")
     ap.add_argument("--eager-steps", type=int, default=2,
-                    help="suites timed with query graphs off (warm_eager_s), after the headline steps")
+                    help="with --full: suites timed with query graphs off (warm_eager_s), after the headline steps")
     ap.add_argument("--profile-adhoc", type=float, default=0.0, metavar="MS",
                     help="diagnostics: cProfile every ad-hoc statement, print those slower than MS")
     ap.add_argument("--param-seed", type=int, default=1000,
                     help="seed of the first ad-hoc parameter stream (stream k uses seed + k)")
     ap.add_argument("--vary-params", type=int, default=2, metavar="STREAMS",
-                    help="suites with fresh TPC-H substitution parameters per query (adhoc_s; 0 = skip)")
+                    help="with --full: suites with fresh TPC-H substitution parameters per query (adhoc_s; 0 = skip)")
     a = ap.parse_args()
+    if a.source is None:
+        a.source = "parquet" if a.full else "hbm"
+    if not a.full:
+        # a plain run times the headline steps only
+        a.eager_steps = a.vary_params = 0
+        a.cpu_check = "off"
 
     if a.gpus < 1:
         print(f"[bench] error: --gpus {a.gpus}", file=sys.stderr)
@@ -251,7 +345,7 @@ def main():
     log(f"[bench] cold suite: {cold_s:.3f}s")
     if cold_per_q:
         log("[bench] cold per query (ms): " + " ".join(f"Q{q}={cold_per_q[q] * 1e3:.1f}" for q in qs))
-    ref = {q: digest(t) for q, t in cold_res.items()}
+    ref = {q: digest(t) for q, t in cold_res.items()} if (a.full or a.digests_out) else {}
     del cold_res
     if a.digests_out and rank == 0:
         with open(a.digests_out, "w") as f:
@@ -286,7 +380,10 @@ def main():
     for s in range(a.steps):
         res = {}
         suite(per_q, res)
-        step_results.append(res)
+        if a.full:
+            step_results.append(res)     # every step's results are digested after the timed region
+        else:
+            step_results[:] = [res]      # only what --dump-outputs writes
         if rank == 0:
             print(f"[bench] step {s}: {time.perf_counter() - t1:.3f}s cumulative", file=sys.stderr, flush=True)
     barrier()
@@ -370,8 +467,12 @@ def main():
             f"{[round(x, 4) for x in adhoc_streams]} s, blocking readbacks {adhoc_readbacks}, modes {adhoc_modes}, "
             f"plans {adhoc_plans}, templates {eng.template_stats}")
 
-    # ---- verification (outside the timed region)
-    mismatches = [(i, q) for i, res in enumerate(step_results) for q, t in res.items() if digest(t) != ref[q]]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_results[-1] if step_results else {})
+
+    # ---- verification (outside the timed region; --full)
+    mismatches = [(i, q) for i, res in enumerate(step_results) for q, t in res.items() if digest(t) != ref[q]] \
+        if a.full else []
     del step_results
     cpu_check = None
     if rank == 0 and (a.cpu_check == "on" or (a.cpu_check == "auto" and a.sf <= 1 and world == 1)) and not a.cpu:
@@ -384,7 +485,8 @@ def main():
         cpu_check = {"queries": len(qs), "mismatched": bad}
         if bad:
             log(f"[bench] CPU check mismatches: {bad}")
-    verified = not mismatches and (cpu_check is None or not cpu_check["mismatched"])
+    # None: a plain run does not digest its results (--full does)
+    verified = (not mismatches and (cpu_check is None or not cpu_check["mismatched"])) if a.full else None
     if mismatches:
         log(f"[bench] result digests differ from the cold run: {mismatches[:10]}")
     scanned = sum(cold_scanned.values())
@@ -414,6 +516,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(step_s * 1e3, 2),
             "higher_is_better": False,
             "scaling": "strong",

@@ -25,6 +25,8 @@ set -o pipefail
 R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R" && mkdir -p gpurun_out
 export TMPDIR=/tmp
+# the log directory of the steps that run bench.py --full (IGLOO_LOG_DIR overrides)
+LOGS="${IGLOO_LOG_DIR:-$R/bench_logs}"; mkdir -p "$LOGS"
 for mode in "$@"; do
   case "$mode" in
     tests)
@@ -32,14 +34,14 @@ for mode in "$@"; do
         -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1
       rc=$?; echo "tests rc=$rc"; tail -2 gpurun_out/pytest_gpu.log ;;
     bench)
-      timeout -k 10 1000 python -u bench.py --steps 20 --warmup 5 --per-query > gpurun_out/bench_sf100.log 2>&1
-      rc=$?; echo "bench rc=$rc"; tail -1 gpurun_out/bench_sf100.log | cut -c1-400 ;;
+      timeout -k 10 1000 python -u bench.py --full --steps 20 --warmup 5 --per-query > "$LOGS/bench_sf100.log" 2>&1
+      rc=$?; echo "bench rc=$rc"; tail -1 "$LOGS/bench_sf100.log" | cut -c1-400 ;;
     spmd)
       timeout -k 10 300 python -u scripts/spmd_world1.py --sf 0.5 --device cuda:0 --backend nccl --runs 6 \
         --json gpurun_out/spmd_sf05.json > gpurun_out/spmd_sf05.log 2>&1
       rc=$?; echo "spmd_world1 rc=$rc"; tail -1 gpurun_out/spmd_sf05.log | cut -c1-300
       [ $rc -eq 0 ] || exit $rc
-      IGLOO_FORCE_SPMD=1 timeout -k 10 900 python -u bench.py --steps 10 --warmup 5 --per-query \
+      IGLOO_FORCE_SPMD=1 timeout -k 10 900 python -u bench.py --full --steps 10 --warmup 5 --per-query \
         > gpurun_out/bench_sf100_spmd1.log 2>&1
       rc=$?; echo "spmd bench rc=$rc"; tail -1 gpurun_out/bench_sf100_spmd1.log | cut -c1-400 ;;
     prof)
@@ -97,6 +99,7 @@ SETS
       # compile the suite's query-specialised kernels at the benchmark scale
       # into gpurun_out/jit_cache (copied into igloo_amd/_jit_cache/ afterwards)
       IGLOO_JIT_CACHE="$R/gpurun_out/jit_cache" IGLOO_JIT_AOT=/nonexistent timeout -k 10 900 python -u bench.py \
+        --full \
         --steps 1 --warmup 1 --eager-steps 0 --vary-params 0 > gpurun_out/jitcache.log 2>&1
       rc=$?; echo "jitcache rc=$rc"; ls gpurun_out/jit_cache | wc -l ;;
     jitsources)
@@ -106,12 +109,14 @@ SETS
       # committed as igloo_amd/jit_sources, compiled ahead of time by build()
       # (igloo_amd/ops/jit.py aot_compile)
       IGLOO_DEBUG="jit_dump=$R/gpurun_out/jit_sources" IGLOO_JIT_AOT=/nonexistent timeout -k 10 900 python -u bench.py \
+        --full \
         --steps 1 --warmup 1 --eager-steps 0 --vary-params 2 --param-seed 7000 > gpurun_out/jitsources.log 2>&1
       rc=$?; echo "jitsources rc=$rc"; ls gpurun_out/jit_sources | wc -l ;;
     jitdiff)
       # generated kernels the timed ad-hoc streams request (to compare with
       # igloo_amd/jit_sources: parameter-dependent kernel sources)
       IGLOO_DEBUG="jit_dump=$R/gpurun_out/jit_b" timeout -k 10 900 python -u bench.py \
+        --full \
         --steps 1 --warmup 1 --eager-steps 0 --vary-params 2 > gpurun_out/jitdiff.log 2>&1
       rc=$?; echo "jitdiff rc=$rc"; ls gpurun_out/jit_b | wc -l ;;
     budget)
@@ -121,12 +126,12 @@ SETS
       rc=$?; echo "budget rc=$rc"; tail -3 gpurun_out/budget_sf${SF:-10}.log ;;
     share2)
       # two ranks sharing the one GPU (gloo collectives, host staged) vs one rank, SF1
-      timeout -k 10 400 python -u bench.py --sf 1 --steps 10 --warmup 3 --per-query \
+      timeout -k 10 400 python -u bench.py --full --sf 1 --steps 10 --warmup 3 --per-query \
         > gpurun_out/bench_sf1_1rank.log 2>&1
       rc=$?; echo "sf1 1-rank rc=$rc"; tail -1 gpurun_out/bench_sf1_1rank.log | cut -c1-200
       [ $rc -eq 0 ] || exit $rc
       IGLOO_BENCH_SHARE_GPU=1 IGLOO_BENCH_DIR=/tmp/igloo_tpch_w2 timeout -k 10 600 python -u -m torch.distributed.run \
-        --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --sf 1 \
+        --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --sf 1 \
         --steps 10 --warmup 3 --per-query > gpurun_out/bench_sf1_2rank_shared.log 2>&1
       rc=$?; echo "sf1 2-rank shared rc=$rc"; tail -1 gpurun_out/bench_sf1_2rank_shared.log | cut -c1-200 ;;
     proj)

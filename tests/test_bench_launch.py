@@ -20,7 +20,8 @@ def _run(args, env=None, timeout=600):
 
 
 def test_bench_self_launches_n_ranks(tmp_path):
-    p = _run(["--cpu", "--gpus", "4", "--sf", "0.01", "--steps", "1", "--warmup", "0", "--eager-steps", "0",
+    # --full: the Parquet data path and the digest verification (``verified``)
+    p = _run(["--full", "--cpu", "--gpus", "4", "--sf", "0.01", "--steps", "1", "--warmup", "0", "--eager-steps", "0",
               "--vary-params", "0", "--data-dir", str(tmp_path)])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -31,6 +32,35 @@ def test_bench_self_launches_n_ranks(tmp_path):
     assert sorted(r["rank"] for r in d["ranks"]) == [0, 1, 2, 3]
     assert all(r["world"] == 4 and r["collectives"] > 0 for r in d["ranks"])
     assert abs(d["value"] - max(r["timed_region_s"] for r in d["ranks"]) / d["steps"]) < 2e-3
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: only the headline steps run (no Parquet dataset, no
+    eager / ad-hoc suites, no digest pass) and --dump-outputs writes the last
+    step's results as float64 arrays, the same from run to run."""
+    import numpy as np
+    dumps = []
+    for tag, steps in (("a", "2"), ("b", "1")):
+        out = tmp_path / tag
+        p = _run(["--cpu", "--gpus", "1", "--sf", "0.01", "--queries", "1,6,13", "--steps", steps, "--warmup", "0",
+                  "--data-dir", str(tmp_path / "data"), "--dump-outputs", str(out)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["full"] is False and d["steps"] == int(steps)
+        assert abs(d["ms_per_step"] - d["value"] * 1e3) < 0.1
+        assert d["warm_eager_s"] is None and d["adhoc_s"] is None and d["verified"] is None
+        assert d["load"] == {"source": "hbm", "datagen_s": d["load"]["datagen_s"]}
+        assert not (tmp_path / "data").exists()          # no dataset written
+        assert p.stderr.count("[bench] step ") == int(steps)
+        man = json.loads((out / "manifest.json").read_text())
+        assert sorted(man) == ["q01", "q06", "q13"] and man["q01"]["rows"] == 4
+        arrays = {c["file"]: np.load(out / c["file"]) for q in man.values() for c in q["columns"]}
+        assert all(v.dtype == np.float64 for v in arrays.values())
+        assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
 
 
 def test_bench_refuses_more_ranks_than_gpus():
