@@ -708,6 +708,79 @@ PYBIND11_MODULE(_native, m) {
   m.def("list_slots", [](int64_t n, int64_t k, uintptr_t se, uintptr_t s) {
     kern::list_slots(n, k, P<int64_t>(se), S(s));
   });
+  m.attr("LIST_FAST_MAX") = (int)kern::kListFastMax;
+  m.def("list_slice_se", [](uintptr_t se, uintptr_t valid, uintptr_t from, uintptr_t from_valid, uintptr_t to,
+                            uintptr_t to_valid, int64_t from_const, int64_t to_const, int64_t n, uintptr_t out_se,
+                            uintptr_t out_valid, uintptr_t s) {
+    kern::list_slice_se(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(from),
+                        P<const uint8_t>(from_valid), P<const int64_t>(to), P<const uint8_t>(to_valid), from_const,
+                        to_const, n, P<int64_t>(out_se), P<uint8_t>(out_valid), S(s));
+  });
+  m.def("list_parts_count", [](uintptr_t parts, int k, int64_t n, uintptr_t out_len, uintptr_t s) {
+    kern::list_parts_count(P<const int64_t>(parts), k, n, P<int64_t>(out_len), S(s));
+  });
+  m.def("list_parts_write", [](uintptr_t parts, int k, int64_t n, uintptr_t offs, int64_t src_n, int64_t cap,
+                               uintptr_t idx, uintptr_t out_se, uintptr_t s) {
+    kern::list_parts_write(P<const int64_t>(parts), k, n, P<const int64_t>(offs), src_n, cap, P<int64_t>(idx),
+                           P<int64_t>(out_se), S(s));
+  });
+  m.def("list_flatten_count", [](uintptr_t se, uintptr_t valid, uintptr_t ise, uintptr_t ivalid, int64_t n,
+                                 int64_t inner_n, uintptr_t out_len, uintptr_t s) {
+    kern::list_flatten_count(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(ise),
+                             P<const uint8_t>(ivalid), n, inner_n, P<int64_t>(out_len), S(s));
+  });
+  m.def("list_flatten_write", [](uintptr_t se, uintptr_t valid, uintptr_t ise, uintptr_t ivalid, int64_t n,
+                                 int64_t inner_n, uintptr_t offs, int64_t child_n, int64_t cap, uintptr_t idx,
+                                 uintptr_t out_se, uintptr_t s) {
+    kern::list_flatten_write(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(ise),
+                             P<const uint8_t>(ivalid), n, inner_n, P<const int64_t>(offs), child_n, cap,
+                             P<int64_t>(idx), P<int64_t>(out_se), S(s));
+  });
+  m.def("list_match_count", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
+                               uintptr_t needle, uintptr_t needle_valid, uintptr_t from, uintptr_t limit,
+                               int64_t limit_const, int mode, int64_t n, uintptr_t out, uintptr_t s) {
+    kern::list_match_count(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
+                           P<const uint8_t>(kvalid), child_n, P<const int64_t>(needle),
+                           P<const uint8_t>(needle_valid), P<const int64_t>(from), P<const int64_t>(limit),
+                           limit_const, mode, n, P<int64_t>(out), S(s));
+  });
+  m.def("list_match_write", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
+                               uintptr_t needle, uintptr_t needle_valid, uintptr_t limit, int64_t limit_const,
+                               int mode, int64_t n, uintptr_t offs, int64_t repl_base, int64_t cap, uintptr_t out,
+                               uintptr_t s) {
+    kern::list_match_write(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
+                           P<const uint8_t>(kvalid), child_n, P<const int64_t>(needle),
+                           P<const uint8_t>(needle_valid), P<const int64_t>(limit), limit_const, mode, n,
+                           P<const int64_t>(offs), repl_base, cap, P<int64_t>(out), S(s));
+  });
+  m.def("list_minmax_idx", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
+                              int is_max, int64_t n, uintptr_t out, uintptr_t s) {
+    kern::list_minmax_idx(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
+                          P<const uint8_t>(kvalid), child_n, is_max, n, P<int64_t>(out), S(s));
+  });
+  m.def("list_set_count", [](uintptr_t seA, uintptr_t validA, uintptr_t keysA, uintptr_t kvalidA, int64_t childA_n,
+                             uintptr_t seB, uintptr_t validB, uintptr_t keysB, uintptr_t kvalidB, int64_t childB_n,
+                             int op, int64_t n, uintptr_t out, uintptr_t s) {
+    kern::list_set_count(P<const int64_t>(seA), P<const uint8_t>(validA), P<const int64_t>(keysA),
+                         P<const uint8_t>(kvalidA), childA_n, P<const int64_t>(seB), P<const uint8_t>(validB),
+                         P<const int64_t>(keysB), P<const uint8_t>(kvalidB), childB_n, op, n, P<int64_t>(out), S(s));
+  });
+  m.def("list_set_write", [](uintptr_t seA, uintptr_t validA, uintptr_t keysA, uintptr_t kvalidA, int64_t childA_n,
+                             uintptr_t seB, uintptr_t validB, uintptr_t keysB, uintptr_t kvalidB, int64_t childB_n,
+                             int op, int64_t n, uintptr_t offs, int64_t b_base, int64_t cap, uintptr_t idx,
+                             uintptr_t s) {
+    kern::list_set_write(P<const int64_t>(seA), P<const uint8_t>(validA), P<const int64_t>(keysA),
+                         P<const uint8_t>(kvalidA), childA_n, P<const int64_t>(seB), P<const uint8_t>(validB),
+                         P<const int64_t>(keysB), P<const uint8_t>(kvalidB), childB_n, op, n,
+                         P<const int64_t>(offs), b_base, cap, P<int64_t>(idx), S(s));
+  });
+  m.def("list_sort_idx", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
+                            int desc, int nulls_first, int64_t n, uintptr_t offs, int64_t cap, uintptr_t idx,
+                            uintptr_t s) {
+    kern::list_sort_idx(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
+                        P<const uint8_t>(kvalid), child_n, desc, nulls_first, n, P<const int64_t>(offs), cap,
+                        P<int64_t>(idx), S(s));
+  });
   m.def("json_parse", [](uintptr_t buf, int64_t start, uintptr_t rows_end, int64_t nrows, uintptr_t cols, int ncols,
                          uintptr_t names, uintptr_t name_off, uintptr_t err, uintptr_t s) {
     if (ncols > 64) throw std::runtime_error("json_parse: at most 64 fields");

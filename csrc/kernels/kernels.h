@@ -429,6 +429,55 @@ void list_element_idx(const int64_t* se, const uint8_t* valid, const int64_t* po
                       int64_t pos_const, int64_t n, int64_t child_n, int64_t* out, hipStream_t s);
 void interleave_idx(int64_t n, int k, int64_t* out, hipStream_t s);
 void list_slots(int64_t n, int64_t k, int64_t* se, hipStream_t s);
+// The list function family. Every kernel reads (start, length) rows with an optional uint8 validity and
+// bounds-checks each child row it emits; rows may alias, overlap or leave parts of the child unreferenced.
+// Elements a quadratic (LDS) kernel handles per list side; longer rows take the generic path (ops/nested.py).
+constexpr int kListFastMax = 512;
+// array_slice / pop_front / pop_back: 1-based inclusive bounds, negative from the end, clamped to the list.
+void list_slice_se(const int64_t* se, const uint8_t* valid, const int64_t* from, const uint8_t* from_valid,
+                   const int64_t* to, const uint8_t* to_valid, int64_t from_const, int64_t to_const, int64_t n,
+                   int64_t* out_se, uint8_t* out_valid, hipStream_t s);
+// k-way per-row concatenation of parts [k][n][3] = (start, length, stride) into one source column: stride 1 a
+// list, 0 a repeated element, -1 a reversed list. count -> exclusive scan -> write (idx: source row or -1).
+void list_parts_count(const int64_t* parts, int k, int64_t n, int64_t* out_len, hipStream_t s);
+// (every write pass bounds its writes by `cap`, the elements of the buffer it was given)
+void list_parts_write(const int64_t* parts, int k, int64_t n, const int64_t* offs, int64_t src_n, int64_t cap,
+                      int64_t* idx, int64_t* out_se, hipStream_t s);
+// flatten: one level of LIST<LIST<T>> (NULL inner lists skipped)
+void list_flatten_count(const int64_t* se, const uint8_t* valid, const int64_t* ise, const uint8_t* ivalid,
+                        int64_t n, int64_t inner_n, int64_t* out_len, hipStream_t s);
+void list_flatten_write(const int64_t* se, const uint8_t* valid, const int64_t* ise, const uint8_t* ivalid,
+                        int64_t n, int64_t inner_n, const int64_t* offs, int64_t child_n, int64_t cap,
+                        int64_t* idx, int64_t* out_se, hipStream_t s);
+// Linear search over an int64 equality key per child element (NULL matches NULL).
+// count mode 0: 1-based position of the first match at or after from (0 = none); 1: matches;
+//            2: length after removing the first `limit` matches
+void list_match_count(const int64_t* se, const uint8_t* valid, const int64_t* keys, const uint8_t* kvalid,
+                      int64_t child_n, const int64_t* needle, const uint8_t* needle_valid, const int64_t* from,
+                      const int64_t* limit, int64_t limit_const, int mode, int64_t n, int64_t* out, hipStream_t s);
+// write mode 0: the 1-based positions of the matches; 1: child rows kept after removing the first `limit`
+// matches; 2: child rows with the first `limit` matches replaced by repl_base + row
+void list_match_write(const int64_t* se, const uint8_t* valid, const int64_t* keys, const uint8_t* kvalid,
+                      int64_t child_n, const int64_t* needle, const uint8_t* needle_valid, const int64_t* limit,
+                      int64_t limit_const, int mode, int64_t n, const int64_t* offs, int64_t repl_base,
+                      int64_t cap, int64_t* out, hipStream_t s);
+// child row of the largest / smallest non-NULL element under an order-preserving key (-1 = none)
+void list_minmax_idx(const int64_t* se, const uint8_t* valid, const int64_t* keys, const uint8_t* kvalid,
+                     int64_t child_n, int is_max, int64_t n, int64_t* out, hipStream_t s);
+// Quadratic kernels: one wave stages a row's keys in LDS (each side <= kListFastMax elements).
+// op 0 distinct(A), 1 union, 2 intersect, 3 except: elements kept, in first-occurrence order, A before B;
+// op 4 has_all (every B element in A), 5 has_any: count only, 0 / 1. B's child rows are emitted + b_base.
+void list_set_count(const int64_t* seA, const uint8_t* validA, const int64_t* keysA, const uint8_t* kvalidA,
+                    int64_t childA_n, const int64_t* seB, const uint8_t* validB, const int64_t* keysB,
+                    const uint8_t* kvalidB, int64_t childB_n, int op, int64_t n, int64_t* out, hipStream_t s);
+void list_set_write(const int64_t* seA, const uint8_t* validA, const int64_t* keysA, const uint8_t* kvalidA,
+                    int64_t childA_n, const int64_t* seB, const uint8_t* validB, const int64_t* keysB,
+                    const uint8_t* kvalidB, int64_t childB_n, int op, int64_t n, const int64_t* offs,
+                    int64_t b_base, int64_t cap, int64_t* idx, hipStream_t s);
+// array_sort: bitonic sort of (null class, order key, position) in LDS; idx[offs[r] + j] = j-th child row
+void list_sort_idx(const int64_t* se, const uint8_t* valid, const int64_t* keys, const uint8_t* kvalid,
+                   int64_t child_n, int desc, int nulls_first, int64_t n, const int64_t* offs, int64_t cap,
+                   int64_t* idx, hipStream_t s);
 
 // ---- json.hip (NDJSON records; rows split by csv_rows with no quote) ------------
 // names / name_off: the schema's field names, packed (ncols <= 64); cols as csv_parse

@@ -140,7 +140,7 @@ std::vector<Token> tokenize(const std::string& t) {
       }
     }
     if (matched) continue;
-    if (std::string("+-*/%=<>(),.;~[]").find(c) != std::string::npos) {
+    if (std::string("+-*/%=<>(),.;~[]:").find(c) != std::string::npos) {
       out.push_back({Token::Op, std::string(1, c), start});
       ++i;
       continue;
@@ -904,6 +904,26 @@ class Parser {
       ++p_;
       if (op == "!=") op = "<>";
       // quantified comparison: x > ALL (subquery) / ANY
+      // over a list expression: x = ANY(l) -> array_has(l, x), x <> ALL(l) -> NOT array_has(l, x)
+      const bool any = (isWord("any") || isWord("some")) && isOp("(", 1);
+      const bool all = isKw("ALL") && isOp("(", 1);
+      if ((any || all) && !isKw("SELECT", 2) && !isKw("WITH", 2)) {
+        if (!((any && op == "=") || (all && op == "<>")))
+          fail("over a list only = ANY(list) and <> ALL(list) are supported");
+        p_ += 2;
+        auto f = make("func", "array_has");
+        f->pos = l->pos;
+        f->kids = {expr(), l};
+        expectOp(")");
+        if (all) {
+          auto n = make("un", "not");
+          n->kids.push_back(f);
+          l = n;
+        } else {
+          l = f;
+        }
+        continue;
+      }
       l = bin(op, l, concat());
     }
     return l;
@@ -955,10 +975,14 @@ class Parser {
         c->kids.push_back(x);
         c->flags["type"] = typeName();
         x = c;
-      } else if (acceptOp("[")) {  // list element (1-based) or struct field by name
+      } else if (acceptOp("[")) {  // list element (1-based), struct field by name, or slice l[a:b]
         auto f = make("func", "array_element");
         f->pos = x->pos;
-        f->kids = {x, expr()};
+        f->kids = {x, isOp(":") ? lit("int", "1") : expr()};
+        while (acceptOp(":")) {   // l[a:b] -> array_slice(l, a, b); a third bound is the stride
+          f->str = "array_slice";
+          f->kids.push_back(isOp("]") ? lit("int", "-1") : expr());
+        }
         expectOp("]");
         x = f;
       } else {

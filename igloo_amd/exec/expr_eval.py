@@ -41,6 +41,13 @@ _JIT_ON_CPU = False   # tests: run the generator (source collection only) on CPU
 
 _NESTED = ("make_array", "struct", "array_length", "array_element", "get_field", "array_has", "array_to_string",
            "regexp_match", "unnest")
+#: the array_* family (ops/nested.py): index arithmetic over (start, length) rows plus one child gather
+_LIST_FAMILY = ("array_slice", "array_pop_front", "array_pop_back", "array_empty", "array_append", "array_prepend",
+                "array_concat", "array_reverse", "array_repeat", "array_resize", "flatten", "array_position",
+                "array_positions", "array_has_expr", "array_has_all", "array_has_any", "array_remove",
+                "array_replace", "array_max", "array_min", "array_distinct", "array_union", "array_intersect",
+                "array_except", "array_sort", "list_cast")
+_NESTED = _NESTED + _LIST_FAMILY
 
 
 class Scalar:
@@ -656,7 +663,44 @@ class Evaluator:
             return Column.from_arrow(pa.array(vals, pa.list_(pa.large_string())), device=dev, dtype=e.dtype)
         if name == "unnest":
             raise ExecutionError("unnest() is only valid as a SELECT list item or in FROM")
+        if name in _LIST_FAMILY:
+            return self._list_family(e, [col(i) for i in range(len(args))])
         raise NotSupported(f"function {name}")
+
+    def _list_family(self, e: Func, c) -> Value:
+        from ..columnar import Nested
+        from ..ops import nested as NS
+        name = e.name
+        if name == "list_cast":
+            a = c[0]
+            kid = a.nested.child
+            cast = Cast(ColRef(0, "child", kid.dtype), e.dtype.child)
+            return Column(e.dtype, a.data, a.valid,
+                          dictionary=Nested(child=self._Cast(cast, Batch({0: kid}, len(kid)))))
+        if name == "array_slice":
+            return NS.slice_(c[0], c[1].data, c[2].data, c[1].valid, c[2].valid)
+        if name in ("array_remove", "array_replace"):
+            return (NS.remove if name == "array_remove" else NS.replace)(*c[:-1], c[-1].data, c[-1].valid)
+        if name == "array_position":
+            return NS.position(c[0], c[1], *((c[2].data, c[2].valid) if len(c) > 2 else ()))
+        if name == "array_repeat":
+            return NS.repeat(c[0], c[1].data, c[1].valid, e.dtype)
+        if name == "array_resize":
+            return NS.resize(c[0], c[1].data, c[1].valid, c[2] if len(c) > 2 else None)
+        if name == "array_concat":
+            return NS.concat_lists(c, e.dtype)
+        if name in ("array_append", "array_prepend"):
+            return NS.append(c[0], c[1], e.dtype, front=name == "array_prepend")
+        if name == "array_sort":
+            return NS.sort(c[0], *e.options)
+        if name in ("array_max", "array_min"):
+            return NS.extreme(c[0], name == "array_max")
+        fn = {"array_pop_front": NS.pop_front, "array_pop_back": NS.pop_back, "array_empty": NS.is_empty,
+              "array_reverse": NS.reverse, "flatten": NS.flatten, "array_positions": NS.positions,
+              "array_has_expr": NS.has_value, "array_has_all": NS.has_all, "array_has_any": NS.has_any,
+              "array_distinct": NS.distinct, "array_union": NS.union, "array_intersect": NS.intersect,
+              "array_except": NS.except_}[name]
+        return fn(*c)
 
     def _func_scalar(self, e: Func, args) -> Scalar:
         vals = [a.value for a in args]
@@ -665,7 +709,7 @@ class Evaluator:
             return Scalar(list(vals), e.dtype)
         if name == "struct":
             return Scalar(dict(zip(e.options, vals)), e.dtype)
-        if any(v is None for v in vals):
+        if any(v is None for v in vals) and name not in _LIST_FAMILY:   # the list family has its own NULL rules
             return Scalar(None, e.dtype)
         if name == "upper":
             return Scalar(vals[0].upper(), T.UTF8)
@@ -880,7 +924,7 @@ def _host_value(c: Column, t: DataType):
     timestamps in microseconds, decimals unscaled)."""
     if c.valid is not None and not bool(c.valid.cpu()[0]):
         return None
-    if t.is_string:
+    if t.is_string or t.is_nested:
         return c.to_arrow()[0].as_py()
     v = c.data.cpu()[0]
     if t.kind == "bool":

@@ -731,6 +731,10 @@ class Binder:
             if op in ("=", "<>", "<", "<=", ">", ">=", "is_distinct_from", "is_not_distinct_from"):
                 return self._cmp(op, l, r)
             if op == "||":
+                if l.dtype.kind == "list" or r.dtype.kind == "list":
+                    both = l.dtype.kind == r.dtype.kind
+                    return self._nested_func("array_concat" if both else
+                                             "array_append" if l.dtype.kind == "list" else "array_prepend", [l, r])
                 return Func("concat", [self._coerce(l, UTF8), self._coerce(r, UTF8)], UTF8)
             if op in ("~", "~*", "!~", "!~*"):
                 # POSIX regex match operators: regexp_like, '*' = case-insensitive
@@ -1251,6 +1255,12 @@ class Binder:
             names = [lit(i, "field name", str) for i in range(0, len(args), 2)]
             vals = args[1::2]
             return Func("struct", list(vals), T.STRUCT(list(zip(names, [a.dtype for a in vals]))), tuple(names))
+        if name in _LIST_FAMILY or (name in ("array_has", "array_contains", "list_has", "list_contains")
+                                    and len(args) == 2 and not isinstance(args[1], Lit)):
+            return self._list_func(_LIST_FAMILY.get(name, "array_has"), name, args)
+        if name in ("array_dims", "list_dims", "string_to_array", "string_to_list", "map", "make_map", "map_keys",
+                    "map_values", "map_extract", "map_entries", "element_at"):
+            raise NotSupported(f"function {name}() (outside the supported list function family)")
         if name in ("array_has", "array_contains", "list_has", "list_contains"):
             a = need_list()
             v = args[1] if len(args) > 1 else None
@@ -1264,6 +1274,8 @@ class Binder:
             null_str = lit(2, "null string", str) if len(args) > 2 else None
             return Func("array_to_string", [a], UTF8, (sep, null_str))
         if name == "unnest":
+            if args and args[0].dtype.kind == "struct":
+                raise NotSupported("unnest() of a struct")
             a = need_list()
             return Func("unnest", [a], a.dtype.child)
         if name == "regexp_match":
@@ -1271,6 +1283,132 @@ class Binder:
             pat = lit(1, "pattern", str)
             flags = lit(2, "flags", str) if len(args) > 2 else ""
             return Func("regexp_match", [a], T.LIST(UTF8), (pat, flags))
+        raise NotSupported(f"function {name}()")
+
+    def _list_func(self, fn: str, name: str, args: List[Expr]) -> Expr:
+        """The array_* family over the (start, length) layout (ops/nested.py).
+        Element arguments are coerced to the list's child type, lists of
+        different child types widened to their common type."""
+        def arity(lo, hi=None):
+            if not lo <= len(args) <= (hi or lo):
+                raise PlanError(f"{name}() takes {lo}{'' if hi in (None, lo) else f' to {hi}'} arguments, "
+                                f"got {len(args)}")
+
+        def lst(i):
+            if args[i].dtype.kind != "list":
+                raise PlanError(f"{name}() needs a list argument, got {args[i].dtype}")
+            return args[i]
+
+        def unify(types):
+            t = None
+            for x in types:
+                if x.kind == "null":
+                    continue
+                if t is None or t == x:
+                    t = x
+                elif t.is_numeric and x.is_numeric and not (t.is_nested or x.is_nested):
+                    t = T.common_numeric(t, x)
+                else:
+                    raise PlanError(f"{name}(): cannot combine {t} and {x}")
+            return t or INT64
+
+        def as_list(e, ct):
+            if e.dtype.child == ct:
+                return e
+            if e.dtype.child.kind == "null" and isinstance(e, Func) and e.name == "make_array":
+                return Func("make_array", [self._coerce(a, ct) for a in e.args], T.LIST(ct))
+            return Func("list_cast", [e], T.LIST(ct))
+
+        def int_arg(i):
+            if not (args[i].dtype.is_integer or args[i].dtype.kind == "null"):
+                raise PlanError(f"{name}(): argument {i + 1} must be an integer, got {args[i].dtype}")
+            return self._coerce(args[i], INT64)
+
+        def flat(a):
+            if a.dtype.child.is_nested:
+                raise NotSupported(f"{name}() on a list whose elements are nested ({a.dtype})")
+            return a
+        if fn == "array_ndims":
+            arity(1)
+            t, d = args[0].dtype, 0
+            while t.kind == "list":
+                t, d = t.child, d + 1
+            return Lit(d, INT64) if d else Lit(None, INT64)
+        if fn == "array_slice":
+            if len(args) == 4:
+                raise NotSupported(f"{name}() with a stride")
+            arity(3)
+            return Func(fn, [lst(0), int_arg(1), int_arg(2)], args[0].dtype)
+        if fn in ("array_pop_front", "array_pop_back", "array_reverse", "array_empty"):
+            arity(1)
+            return Func(fn, [lst(0)], BOOL if fn == "array_empty" else args[0].dtype)
+        if fn in ("array_distinct", "array_max", "array_min"):
+            arity(1)
+            a = flat(lst(0))
+            return Func(fn, [a], a.dtype if fn == "array_distinct" else a.dtype.child)
+        if fn == "array_sort":
+            arity(1, 3)
+            a = flat(lst(0))
+            opts = []
+            for i, words in ((1, ("ASC", "DESC")), (2, ("NULLS FIRST", "NULLS LAST"))):
+                w = words[0]
+                if len(args) > i:
+                    w = TPL.peek(args[i]) if isinstance(args[i], Lit) else None
+                    if not isinstance(w, str) or w.upper() not in words:
+                        raise PlanError(f"{name}(): argument {i + 1} must be one of {', '.join(words)}")
+                opts.append(w.upper() == words[0])
+            return Func(fn, [a], a.dtype, (not opts[0], opts[1]))
+        if fn in ("array_append", "array_prepend"):
+            arity(2)
+            a, x = (lst(0), args[1]) if fn == "array_append" else (lst(1), args[0])
+            ct = unify([a.dtype.child, x.dtype])
+            return Func(fn, [as_list(a, ct), self._coerce(x, ct)], T.LIST(ct))
+        if fn in ("array_concat", "array_union", "array_intersect", "array_except", "array_has_all", "array_has_any"):
+            if fn == "array_concat":
+                if len(args) < 2:
+                    raise PlanError(f"{name}() takes at least 2 lists")
+            else:
+                arity(2)
+            ls = [lst(i) for i in range(len(args))]
+            ct = unify([a.dtype.child for a in ls])
+            ls = [as_list(a, ct) for a in ls]
+            if fn != "array_concat":
+                [flat(a) for a in ls]
+            return Func(fn, ls, BOOL if fn in ("array_has_all", "array_has_any") else T.LIST(ct))
+        if fn == "array_repeat":
+            arity(2)
+            return Func(fn, [args[0] if args[0].dtype.kind != "null" else Lit(None, INT64), int_arg(1)],
+                        T.LIST(args[0].dtype if args[0].dtype.kind != "null" else INT64))
+        if fn == "array_resize":
+            arity(2, 3)
+            a = lst(0)
+            rest = [int_arg(1)]
+            if len(args) == 3:
+                ct = unify([a.dtype.child, args[2].dtype])
+                a = as_list(a, ct)
+                rest.append(self._coerce(args[2], ct))
+            return Func(fn, [a] + rest, a.dtype)
+        if fn == "flatten":
+            arity(1)
+            a = lst(0)
+            if a.dtype.child.kind != "list":
+                raise PlanError(f"flatten() needs a list of lists, got {a.dtype}")
+            return Func(fn, [a], a.dtype.child)
+        if fn in ("array_position", "array_positions", "array_has"):
+            arity(2, 3 if fn == "array_position" else 2)
+            a = flat(lst(0))
+            ct = unify([a.dtype.child, args[1].dtype])
+            out = [as_list(a, ct), self._coerce(args[1], ct)] + ([int_arg(2)] if len(args) == 3 else [])
+            return Func("array_has_expr" if fn == "array_has" else fn, out,
+                        {"array_position": INT64, "array_positions": T.LIST(INT64), "array_has": BOOL}[fn])
+        if fn in ("array_remove", "array_replace"):
+            k = 2 if fn == "array_remove" else 3
+            suffix = name.rsplit("_", 1)[-1]
+            limit = [int_arg(k)] if suffix == "n" else [Lit((1 << 63) - 1 if suffix == "all" else 1, INT64)]
+            arity(k + 1 if suffix == "n" else k)
+            a = flat(lst(0))
+            ct = unify([a.dtype.child] + [x.dtype for x in args[1:k]])
+            return Func(fn, [as_list(a, ct)] + [self._coerce(x, ct) for x in args[1:k]] + limit, T.LIST(ct))
         raise NotSupported(f"function {name}()")
 
     def _agg_order(self, node, scope) -> List[Tuple[Expr, bool, bool]]:
@@ -1638,7 +1776,32 @@ _TRUNC_UNITS = ("microsecond", "millisecond", "second", "minute", "hour", "day",
 _NESTED_FUNCS = ("make_array", "make_list", "array", "array_length", "cardinality", "list_length", "array_size",
                  "array_element", "list_element", "array_extract", "list_extract", "get_field", "struct",
                  "named_struct", "array_has", "array_contains", "list_has", "list_contains", "array_to_string",
-                 "list_to_string", "array_join", "list_join", "unnest", "regexp_match")
+                 "list_to_string", "array_join", "list_join", "unnest", "regexp_match", "array_dims", "list_dims",
+                 "string_to_array", "string_to_list", "map", "make_map", "map_keys", "map_values", "map_extract",
+                 "map_entries", "element_at")
+
+
+def _list_family() -> dict:
+    """SQL name -> canonical function of the array_* family (DataFusion's
+    list_* aliases included)."""
+    names = {"array_slice": (), "array_pop_front": (), "array_pop_back": (), "array_empty": ("empty",),
+             "array_ndims": (), "array_append": ("array_push_back",), "array_prepend": ("array_push_front",),
+             "array_concat": ("array_cat",), "array_reverse": (), "array_repeat": (), "array_resize": (),
+             "flatten": (), "array_position": ("array_indexof",), "array_positions": (),
+             "array_has_all": (), "array_has_any": (), "array_remove": ("array_remove_n", "array_remove_all"),
+             "array_replace": ("array_replace_n", "array_replace_all"), "array_max": (), "array_min": (),
+             "array_distinct": (), "array_union": (), "array_intersect": (), "array_except": (), "array_sort": ()}
+    out = {}
+    for fn, aliases in names.items():
+        for a in (fn,) + aliases:
+            out[a] = fn
+            if a.startswith("array_"):
+                out["list_" + a[len("array_"):]] = fn
+    return out
+
+
+_LIST_FAMILY = _list_family()
+_NESTED_FUNCS = _NESTED_FUNCS + tuple(_LIST_FAMILY)
 
 
 def similar_to_regex(pat: str, esc: str = "\\") -> str:
