@@ -8,12 +8,17 @@
 //     f64, counts, nearest-head index, head counts), forward or reverse. Three
 //     phases (tile reduce -> carry scan over tiles -> tile rescan) with the
 //     segmented operator (f1,v1)+(f2,v2) = (f1|f2, f2 ? v2 : v1 op v2) carried
-//     through wave64 shuffles, so it is exact for any segment layout.
+//     through wave64 shuffles, so it is exact for any segment layout. int64
+//     sums wrap; the overflow flag is raised only by the final per-row pass,
+//     where it is exact: set iff some row's running sum leaves int64. f64
+//     min / max follow the total order of f64_ord (NaN above +inf), as the
+//     GROUP BY aggregates do.
 //   * win_bounds: per-row frame [lo, hi] for ROWS / RANGE / GROUPS frames;
 //     RANGE offsets binary-search the sorted ORDER BY key inside the
 //     partition's non-NULL block.
 //   * win_frame_sum: framed sum + count as a difference of global prefixes.
-//   * win_frame_minmax: framed min / max by a loop over the frame.
+//   * win_frame_minmax: framed min / max by a loop over the frame (narrow
+//     frames) or a sparse table (win_sparse_*), both in the f64_ord order.
 //   * win_rank / win_index: ranking functions and the source row of
 //     lag / lead / first_value / last_value / nth_value.
 // Parity: DataFusion's WindowAggExec / BoundedWindowAggExec, reached by the
@@ -30,9 +35,16 @@ namespace {
 constexpr int kWItems = 8;
 constexpr int kWTile = kBlock * kWItems;
 
+// Order-preserving int64 image of an f64 bit pattern (its own inverse):
+// -inf < ... < -0.0 < +0.0 < ... < +inf < NaN. (NaNs with the sign bit set
+// would sort below -inf; the engine produces none.)
+__device__ inline int64_t f64_ord(int64_t bits) { return bits >= 0 ? bits : (bits ^ INT64_MAX); }
+
 template <int OP>
 struct WOp;
 // 0 sum int64 (wrapping, overflow flagged), 1 sum f64, 2 min i64, 3 max i64, 4 min f64, 5 max f64
+// (f64 min / max compare f64_ord images: NaN is the greatest value, so the
+// identity of min is the topmost image, a NaN)
 template <>
 struct WOp<0> {
   static __device__ int64_t id() { return 0; }
@@ -61,19 +73,13 @@ struct WOp<3> {
 };
 template <>
 struct WOp<4> {
-  static __device__ int64_t id() { return __builtin_bit_cast(int64_t, __builtin_huge_val()); }
-  static __device__ int64_t ap(int64_t a, int64_t b, bool&) {
-    double x = __builtin_bit_cast(double, a), y = __builtin_bit_cast(double, b);
-    return __builtin_bit_cast(int64_t, y < x ? y : x);
-  }
+  static __device__ int64_t id() { return INT64_MAX; }
+  static __device__ int64_t ap(int64_t a, int64_t b, bool&) { return f64_ord(b) < f64_ord(a) ? b : a; }
 };
 template <>
 struct WOp<5> {
   static __device__ int64_t id() { return __builtin_bit_cast(int64_t, -__builtin_huge_val()); }
-  static __device__ int64_t ap(int64_t a, int64_t b, bool&) {
-    double x = __builtin_bit_cast(double, a), y = __builtin_bit_cast(double, b);
-    return __builtin_bit_cast(int64_t, y > x ? y : x);
-  }
+  static __device__ int64_t ap(int64_t a, int64_t b, bool&) { return f64_ord(b) > f64_ord(a) ? b : a; }
 };
 
 struct ScanArgs {
@@ -287,15 +293,22 @@ __global__ __launch_bounds__(kBlock) void seg_scan_down(ScanArgs a, const int* t
   block_seg_scan<OP>(f, v, ef, ev, tf, tv, ovf, sf, sv);
   int64_t acc = ev;
   if (use_carry && !ef) acc = WOp<OP>::ap(tval[blockIdx.x], ev, ovf);
+  // Only this per-row pass decides the overflow flag. The partial sums above
+  // (a thread's rows, a wave, a tile) may wrap although every running sum
+  // fits, so their flag is dropped. Here `acc` is the running sum mod 2^64:
+  // at the first row whose true running sum leaves int64 the previous one
+  // fitted, `acc` equals it, and the add overflows; and an add that overflows
+  // on a true running sum is an overflow. So the flag is exact.
+  bool row_ovf = false;
 #pragma unroll
   for (int j = 0; j < kWItems; ++j) {
     const int64_t k = base + j;
     if (k < a.n) {
-      acc = hs[j] ? xs[j] : WOp<OP>::ap(acc, xs[j], ovf);
+      acc = hs[j] ? xs[j] : WOp<OP>::ap(acc, xs[j], row_ovf);
       out[a.reverse ? a.n - 1 - k : k] = acc;
     }
   }
-  if (OP == 0 && ovf && err != nullptr) *err = 1;
+  if (OP == 0 && row_ovf && err != nullptr) *err = 1;
 }
 
 template <int OP>
@@ -468,19 +481,19 @@ __global__ __launch_bounds__(kBlock) void win_frame_minmax_kernel(const int64_t*
   if (r >= n) return;
   bool any = false;
   int64_t bi = 0;
-  double bf = 0;
   for (int64_t j = lo[r]; j <= hi[r]; ++j) {
     if (valid != nullptr && !valid[j]) continue;
     if (F64) {
-      double x = __builtin_bit_cast(double, vals[j]);
-      if (!any || (MAX ? x > bf : x < bf)) bf = x;
+      // compared as f64_ord images: NaN is the greatest value
+      int64_t x = f64_ord(vals[j]);
+      if (!any || (MAX ? x > bi : x < bi)) bi = x;
     } else {
       int64_t x = vals[j];
       if (!any || (MAX ? x > bi : x < bi)) bi = x;
     }
     any = true;
   }
-  out[r] = F64 ? __builtin_bit_cast(int64_t, bf) : bi;
+  out[r] = F64 ? f64_ord(bi) : bi;
   out_valid[r] = any;
 }
 
@@ -489,8 +502,7 @@ __global__ __launch_bounds__(kBlock) void win_frame_minmax_kernel(const int64_t*
 // one pass over the previous one; a frame [lo, hi] is covered by two
 // overlapping power-of-two blocks. NULLs enter as the op's identity; the
 // frame's NULL-free flag comes from the caller's prefix count (or hi >= lo).
-// Floats travel as order-preserving int64 images.
-__device__ inline int64_t f64_ord(int64_t bits) { return bits >= 0 ? bits : (bits ^ INT64_MAX); }
+// Floats travel as order-preserving int64 images (f64_ord).
 
 __global__ __launch_bounds__(kBlock) void win_sparse_init_kernel(const int64_t* __restrict__ vals, bool f64,
                                                                  const uint8_t* __restrict__ valid, int64_t n,

@@ -18,7 +18,10 @@ segmented scan or an elementwise pass over the sorted order
 * sliding ROWS / RANGE / GROUPS frames: per-row [lo, hi] bounds (RANGE
   offsets binary-search the sorted key), sums and counts as differences of
   global prefixes, min / max by a frame loop (or a one-sided scan when the
-  frame is unbounded on one side);
+  frame is unbounded on one side). An int64 SUM raises the overflow error
+  if and only if some output row's exact sum lies outside int64: the scans
+  flag exactly that for running ROWS frames, and the other frames sum
+  32-bit halves;
 * lag / lead / first_value / last_value / nth_value: a source-row index
   per row and one gather.
 
@@ -331,7 +334,8 @@ def _aggregate(w: WindowCall, b: Batch, st: _Sorted, lo, hi, ctx) -> Column:
     else:
         read = "frame"
     pid = st.pid
-    err = torch.zeros(1, dtype=torch.int32, device=dev) if dev.type == "cuda" else None
+    # set iff an int64 SUM's exact value lies outside int64 (both devices)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def scan(vals, vkind, op, vv=valid):
         if read == "frame":
@@ -340,15 +344,34 @@ def _aggregate(w: WindowCall, b: Batch, st: _Sorted, lo, hi, ctx) -> Column:
         return _at(r, read)
 
     def prefix(vals, vkind, op, vv=valid):
-        return W.seg_scan(None, vals, vkind, op, n, valid=vv, device=dev, err=err)
+        # the global prefix of a framed sum may wrap (frame_sum takes the
+        # difference mod 2^64): its overflow says nothing about a frame
+        return W.seg_scan(None, vals, vkind, op, n, valid=vv, device=dev)
+
+    def sum_i64(vals):
+        """int64 sums with an exact overflow test on the rows that are read.
+        A running ROWS frame reads every row of the scan, whose own flag is
+        exact. The other frames read only some rows (or differences of a
+        global prefix), so a running sum nobody reads may overflow: they sum
+        the two 32-bit halves, whose scans cannot wrap (n < 2^31), and the
+        carry-joined top word says whether the sum fits."""
+        if read is None:
+            return scan(vals, W.V_I64, W.SUM_I)
+        halves = [(vals & 0xFFFFFFFF).contiguous(), (vals >> 32).contiguous()]
+        if read == "frame":
+            s0, s1 = [W.frame_sum(prefix(x, W.V_I64, W.SUM_I), None, lo, hi, n)[0] for x in halves]
+        else:
+            s0, s1 = [_at(W.seg_scan(pid, x, W.V_I64, W.SUM_I, n, valid=valid, device=dev), read) for x in halves]
+        top = s1 + (s0 >> 32)
+        err.logical_or_(((top < -2**31) | (top >= 2**31)).any().reshape(1))
+        return (top << 32) | (s0 & 0xFFFFFFFF)
 
     def counts():
         if read != "frame":
             return scan(None, W.V_ONE, W.SUM_I)
         return W.frame_sum(None, prefix(None, W.V_ONE, W.SUM_I), lo, hi, n)[1]
 
-    if err is not None:
-        ctx.deferred_checks.append((err, f"window {f}() overflowed 64-bit integer arithmetic"))
+    ctx.deferred_checks.append((err, f"window {f}() overflowed 64-bit integer arithmetic"))
     if f == "count":
         return Column(T.INT64, counts())
     src = col.dtype
@@ -383,7 +406,9 @@ def _aggregate(w: WindowCall, b: Batch, st: _Sorted, lo, hi, ctx) -> Column:
             vals = vals.to(torch.int64)
         vk = W.V_F64 if fl else (W.V_I32 if vals.dtype == torch.int32 else W.V_I64)
         op = W.SUM_F if fl else W.SUM_I
-        if read != "frame":
+        if vk == W.V_I64:
+            s = sum_i64(vals)
+        elif read != "frame":
             s = scan(vals, vk, op)
         else:
             s = W.frame_sum(prefix(vals, vk, op), None, lo, hi, n)[0]

@@ -27,6 +27,7 @@ _I64MIN, _I64MAX = -2**63, 2**63 - 1
 
 
 def _identity(op: int):
+    # (MIN_F / MAX_F scan ordered int64 images on the host path and take their identities there)
     return {SUM_I: 0, SUM_F: 0.0, MIN_I: _I64MAX, MAX_I: _I64MIN, MIN_F: float("inf"), MAX_F: float("-inf")}[op]
 
 
@@ -38,15 +39,29 @@ def seg_scan(ids: Optional[torch.Tensor], vals: Optional[torch.Tensor], vkind: i
     (``vals`` int64 / int32 / f64), 1 per row (V_ONE), the row index at heads
     of ``ids2`` (V_HEADIDX) or a 0/1 head flag of ``ids2`` (V_HEAD2). NULL
     rows (``valid`` False) contribute the operator's identity (0 for counts).
-    Returns int64, or float64 for the f64 operators. ``err`` (int32 [1]):
-    set when an int64 sum overflows."""
+    f64 min / max follow the total order -inf < ... < +inf < NaN (the order of
+    the GROUP BY aggregates), so the identity of MIN_F is a NaN.
+    Returns int64, or float64 for the f64 operators. int64 sums wrap; ``err``
+    (int32 [1]) is set if and only if some row's running sum (in scan order,
+    inside its segment) lies outside int64, on both devices."""
     ref = next((t for t in (ids, vals, ids2, valid) if t is not None), None)
     dev = ref.device if ref is not None else torch.device(device or "cpu")
     f64 = op in (SUM_F, MIN_F, MAX_F)
     if n == 0:
         return torch.zeros(0, dtype=torch.float64 if f64 else torch.int64, device=dev)
     if not dev.type == "cuda":
-        return _seg_scan_cpu(ids, vals, vkind, op, n, valid, ids2, reverse)
+        out = _seg_scan_cpu(ids, vals, vkind, op, n, valid, ids2, reverse)
+        if err is not None and op == SUM_I and vkind == V_I64:
+            # exact overflow test: the scans of the two 32-bit halves cannot
+            # overflow (n < 2^31), and their carry-joined top word says whether
+            # the running sum fits
+            v = vals.to(torch.int64)
+            s0 = _seg_scan_cpu(ids, v & 0xFFFFFFFF, V_I64, SUM_I, n, valid, ids2, reverse)
+            s1 = _seg_scan_cpu(ids, v >> 32, V_I64, SUM_I, n, valid, ids2, reverse)
+            top = s1 + (s0 >> 32)
+            if bool(((top < -2**31) | (top >= 2**31)).any()):
+                err.fill_(1)
+        return out
     N = launch("win_seg_scan")
     tiles = N.win_scan_tiles(n)
     tflag = torch.empty(max(tiles, 1), dtype=torch.int32, device=dev)
@@ -87,10 +102,15 @@ def _seg_scan_cpu(ids, vals, vkind, op, n, valid, ids2, reverse) -> torch.Tensor
         v = torch.where(_heads(ids2, order, n), order, torch.full((n,), ident, dtype=torch.int64))
     else:
         v = _heads(ids2, order, n).to(torch.int64)
+    ordered = op in (MIN_F, MAX_F)
+    if ordered:
+        # total order of the kernels (NaN above +inf): scan the int64 images
+        v = _f64_ord(v.to(torch.float64).contiguous().view(torch.int64))
+        ident = _I64MAX if op == MIN_F else int(_f64_ord(torch.tensor(float("-inf")).double().view(torch.int64)))
     if valid is not None:
         z = 0 if vkind in (V_ONE, V_HEAD2) else ident
         v = torch.where(valid[order], v, torch.full_like(v, z))
-    if f64:
+    if f64 and not ordered:
         v = v.to(torch.float64)
     # Hillis-Steele segmented scan: (f1,v1)+(f2,v2) = (f1|f2, f2 ? v2 : v1 op v2)
     f = h.clone()
@@ -111,7 +131,21 @@ def _seg_scan_cpu(ids, vals, vkind, op, n, valid, ids2, reverse) -> torch.Tensor
         d *= 2
     out = torch.empty_like(v)
     out[order] = v
-    return out
+    return _f64_ord(out).view(torch.float64) if ordered else out
+
+
+def _f64_ord(bits: torch.Tensor) -> torch.Tensor:
+    """Order-preserving int64 image of f64 bit patterns (window.hip f64_ord;
+    its own inverse): -inf < ... < -0.0 < +0.0 < ... < +inf < NaN."""
+    return torch.where(bits >= 0, bits, bits ^ _I64MAX)
+
+
+def _sat_add(a: torch.Tensor, o: int) -> torch.Tensor:
+    """a + o on int64, saturating instead of wrapping (window.hip sat_add)."""
+    s = a + o
+    if o >= 0:
+        return torch.where(s < a, torch.full_like(a, _I64MAX), s)
+    return torch.where(s > a, torch.full_like(a, _I64MIN), s)
 
 
 def bounds(n: int, ss, se, ps, pe, unit: str, skind: str, soff, ekind: str, eoff, key=None, key_valid=None,
@@ -152,13 +186,13 @@ def bounds(n: int, ss, se, ps, pe, unit: str, skind: str, soff, ekind: str, eoff
         hi = r.clone() if unit == "rows" else pe.clone()
     if unit == "rows":
         if sk == 1:
-            lo = r - _i(soff)
+            lo = _sat_add(r, -_i(soff))
         elif sk == 3:
-            lo = r + _i(soff)
+            lo = _sat_add(r, _i(soff))
         if ek == 1:
-            hi = r - _i(eoff)
+            hi = _sat_add(r, -_i(eoff))
         elif ek == 3:
-            hi = r + _i(eoff)
+            hi = _sat_add(r, _i(eoff))
     elif unit == "range" and (sk in (1, 3) or ek in (1, 3)):
         lo, hi = _range_cpu(n, s0, e0, ps, pe, sk, soff, ek, eoff, key, key_valid, desc, lo, hi)
     elif unit == "groups":
@@ -169,13 +203,13 @@ def bounds(n: int, ss, se, ps, pe, unit: str, skind: str, soff, ekind: str, eoff
             gg = g - _i(soff)
             lo = torch.where(gg < g0, s0, gpos[gg.clamp(min=0)])
         elif sk == 3:
-            gg = g + _i(soff)
+            gg = _sat_add(g, _i(soff))
             lo = torch.where(gg > g1, e0 + 1, gpos[gg.clamp(max=ngroups - 1)])
         if ek == 1:
             gg = g - _i(eoff)
             hi = torch.where(gg < g0, s0 - 1, gend[gg.clamp(min=0)])
         elif ek == 3:
-            gg = g + _i(eoff)
+            gg = _sat_add(g, _i(eoff))
             hi = torch.where(gg > g1, e0, gend[gg.clamp(max=ngroups - 1)])
     return torch.maximum(lo, s0), torch.minimum(hi, e0)
 
@@ -211,8 +245,9 @@ def _range_cpu(n, s0, e0, ps, pe, sk, soff, ek, eoff, key, key_valid, desc, lo, 
 
     def shift(forward, off):
         up = forward != desc
-        o = float(off) if f64 else int(off)
-        return k + o if up else k - o
+        if f64:
+            return k + float(off) if up else k - float(off)
+        return _sat_add(k, int(off) if up else -int(off))
     if sk == 1:
         lo = _search(k, nb, ne, shift(False, soff), desc, False)
     elif sk == 3:
@@ -232,7 +267,10 @@ def _range_cpu(n, s0, e0, ps, pe, sk, soff, ek, eoff, key, key_valid, desc, lo, 
 
 def frame_sum(psum: Optional[torch.Tensor], pcnt: Optional[torch.Tensor], lo, hi, n: int):
     """Framed sum and count from inclusive global prefixes (sum: int64
-    wrapping or f64)."""
+    wrapping or f64). The int64 difference is taken mod 2^64, so prefixes
+    that have wrapped still give the exact frame sum whenever that sum fits;
+    nothing here reports a frame sum that does not (exec/window.py sums
+    32-bit halves where that can happen)."""
     if n == 0 or not lo.is_cuda:
         empty = hi < lo
         li = (lo - 1).clamp(min=0)
@@ -260,7 +298,9 @@ def frame_minmax(vals: torch.Tensor, valid: Optional[torch.Tensor], lo, hi, n: i
     """min / max over each row's frame [lo, hi] -> (values, valid). Narrow
     frames: a loop over the frame; wider ones: a sparse table of
     ceil(log2(width)) levels (one pass each) and two reads per row, so a
-    ``ROWS BETWEEN 100000 PRECEDING`` frame costs O(n log w), not O(n w)."""
+    ``ROWS BETWEEN 100000 PRECEDING`` frame costs O(n log w), not O(n w).
+    Floats follow the total order of ``seg_scan`` (NaN above +inf) on every
+    path. NULL rows are skipped; a frame without a value is invalid."""
     f64 = vals.dtype.is_floating_point
     if n == 0:
         return torch.zeros(0, dtype=torch.float64 if f64 else torch.int64, device=lo.device), \
@@ -289,8 +329,9 @@ def frame_minmax(vals: torch.Tensor, valid: Optional[torch.Tensor], lo, hi, n: i
         del table
         return (out.view(torch.float64) if f64 else out), ov
     # host: the same sparse table with torch ops
-    ident = float("-inf") if (is_max and f64) else float("inf") if f64 else (-(2**63) if is_max else 2**63 - 1)
-    cur = v.clone()
+    # (floats as their ordered int64 images, like the kernels: NaN is the greatest value)
+    ident = _I64MIN if is_max else _I64MAX
+    cur = _f64_ord(v.view(torch.int64)) if f64 else v.clone()
     if valid is not None:
         cur = torch.where(valid, cur, torch.full_like(cur, ident))
     tabs = [cur]
@@ -315,6 +356,8 @@ def frame_minmax(vals: torch.Tensor, valid: Optional[torch.Tensor], lo, hi, n: i
         cnt = pcnt[hi.clamp(0, n - 1)] - torch.where(lo > 0, pcnt[(lo - 1).clamp(min=0)], torch.zeros_like(lo))
         ok = ok & (cnt > 0)
     out = torch.where(ok, out, torch.zeros_like(out))
+    if f64:
+        out = torch.where(ok, _f64_ord(out), out).view(torch.float64)
     return out, ok
 
 
