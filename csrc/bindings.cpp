@@ -733,6 +733,22 @@ PYBIND11_MODULE(_native, m) {
     kern::list_slots(n, k, P<int64_t>(se), S(s));
   });
   m.attr("LIST_FAST_MAX") = (int)kern::kListFastMax;
+  m.def("map_lookup_idx", [](uintptr_t se, uintptr_t valid, int64_t n, int64_t child_n, int key_width, uintptr_t keys,
+                             uintptr_t kvalid, uintptr_t needle, uintptr_t needle_valid, int64_t needle_const,
+                             uintptr_t out, uintptr_t s) {
+    kern::map_lookup_idx(P<const int64_t>(se), P<const uint8_t>(valid), n, child_n, key_width, P<const void>(keys),
+                         P<const uint8_t>(kvalid), P<const int64_t>(needle), P<const uint8_t>(needle_valid),
+                         needle_const, P<int64_t>(out), S(s));
+  });
+  m.def("map_lookup_idx_str", [](uintptr_t se, uintptr_t valid, int64_t n, int64_t child_n, uintptr_t key_offs,
+                                 uintptr_t key_bytes, int64_t key_nbytes, uintptr_t kvalid, uintptr_t needle_offs,
+                                 uintptr_t needle_bytes, int64_t needle_nbytes, uintptr_t needle_valid,
+                                 int64_t const_len, int64_t const_stride, uintptr_t out, uintptr_t s) {
+    kern::map_lookup_idx_str(P<const int64_t>(se), P<const uint8_t>(valid), n, child_n, P<const int64_t>(key_offs),
+                             P<const uint8_t>(key_bytes), key_nbytes, P<const uint8_t>(kvalid),
+                             P<const int64_t>(needle_offs), P<const uint8_t>(needle_bytes), needle_nbytes,
+                             P<const uint8_t>(needle_valid), const_len, const_stride, P<int64_t>(out), S(s));
+  });
   m.def("list_slice_se", [](uintptr_t se, uintptr_t valid, uintptr_t from, uintptr_t from_valid, uintptr_t to,
                             uintptr_t to_valid, int64_t from_const, int64_t to_const, int64_t n, uintptr_t out_se,
                             uintptr_t out_valid, uintptr_t s) {

@@ -453,6 +453,21 @@ void list_element_idx(const int64_t* se, const uint8_t* valid, const int64_t* po
                       int64_t pos_const, int64_t n, int64_t child_n, int64_t* out, hipStream_t s);
 void interleave_idx(int64_t n, int k, int64_t* out, hipStream_t s);
 void list_slots(int64_t n, int64_t k, int64_t* se, hipStream_t s);
+// MAP rows share the LIST layout over two equally long children (key, value). out[r] = child row of the
+// first entry of row r whose key equals the needle, -1 for none (no match, NULL row, NULL needle, malformed
+// slot). Fixed-width keys of key_width 1/2/4/8 bytes compare sign-extended against an int64 needle: a
+// per-row tensor with validity, or needle_const when needle is null.
+void map_lookup_idx(const int64_t* se, const uint8_t* valid, int64_t n, int64_t child_n, int key_width,
+                    const void* keys, const uint8_t* kvalid, const int64_t* needle, const uint8_t* needle_valid,
+                    int64_t needle_const, int64_t* out, hipStream_t s);
+// Plain UTF-8 keys (int64 offsets + bytes). The needle is a per-row plain string column (needle_offs set) or
+// a constant of const_len bytes: needle_bytes then holds 4 copies, copy m at byte m * const_stride + m of a
+// 4-byte aligned buffer, so a key at any alignment compares dword by dword with the copy that shares it.
+void map_lookup_idx_str(const int64_t* se, const uint8_t* valid, int64_t n, int64_t child_n, const int64_t* key_offs,
+                        const uint8_t* key_bytes, int64_t key_nbytes, const uint8_t* kvalid,
+                        const int64_t* needle_offs, const uint8_t* needle_bytes, int64_t needle_nbytes,
+                        const uint8_t* needle_valid, int64_t const_len, int64_t const_stride, int64_t* out,
+                        hipStream_t s);
 // The list function family. Every kernel reads (start, length) rows with an optional uint8 validity and
 // bounds-checks each child row it emits; rows may alias, overlap or leave parts of the child unreferenced.
 // Elements a quadratic (LDS) kernel handles per list side; longer rows take the generic path (ops/nested.py).

@@ -1,4 +1,4 @@
-// LIST / STRUCT column helpers (DataFusion's datafusion-functions-nested,
+// LIST / STRUCT / MAP column helpers (DataFusion's datafusion-functions-nested,
 // reference Cargo.lock:1125, reached through SessionContext::sql at
 // crates/engine/src/lib.rs:54-57).
 //
@@ -29,8 +29,13 @@
 // element data moves before that gather. Rows may alias, overlap, start anywhere and
 // leave child rows unreferenced: nothing here assumes lists tile the child, and every
 // emitted row is checked against the child's length, every write against its buffer.
-// Not here: a slice stride, array_dims, string_to_array, MAP, unnest(struct), ordering
-// or equality of nested elements (the binder answers NotSupported).
+// MAP rows are the same (start, length) pairs over two equally long children (key, value), so
+// map_keys / map_values / map_entries / cardinality need no kernel;
+//   map_lookup_idx    m[k] / element_at / map_extract: child row of the first entry whose key
+//                     equals a constant or per-row needle, keys compared where they lie (fixed
+//                     width at their own size, plain UTF-8 by length, then dwords and a byte tail)
+// Not here: a slice stride, array_dims, string_to_array, unnest(struct), unnest(map), ordering
+// or equality of nested elements and maps (the binder answers NotSupported).
 #include "common.h"
 #include "kernels.h"
 
@@ -683,6 +688,131 @@ __global__ __launch_bounds__(kBlock) void list_sort_kernel(SortOp f) {
   for_wave_tiles(f.n, kListShort, f);
 }
 
+// ---- map lookup ----------------------------------------------------------------------
+// m[k] / element_at / map_extract: the child row of the first entry of the row whose key equals
+// the needle, -1 for none (no match, NULL map row, NULL needle, malformed slot). Keys are read
+// where they lie: fixed-width keys at their native width against an int64 needle, plain UTF-8
+// keys by length first and bytes after. Rows of at most a wave's width run one lane per row;
+// longer rows are strided by the wave and the lowest matching lane of the first matching stride
+// wins, so duplicate keys (imported, unvalidated maps) resolve to the first entry.
+template <class K>
+struct FixedKeys {
+  const K* keys;
+  const uint8_t* kvalid;
+  const int64_t* needle;        // per row, or null: needle_const
+  const uint8_t* needle_valid;
+  int64_t needle_const;
+  using Needle = int64_t;
+  __device__ bool load(int64_t r, Needle& nd) const {
+    if (!needle) {
+      nd = needle_const;
+      return true;
+    }
+    nd = needle[r];
+    return row_ok(needle_valid, r);
+  }
+  __device__ bool hit(int64_t c, const Needle& nd) const { return (!kvalid || kvalid[c]) && (int64_t)keys[c] == nd; }
+};
+
+// len bytes at a and b are equal: dwords where both pointers reach 4-byte alignment together
+// (entries start at arbitrary byte offsets), bytes for the head, the tail and everything else
+__device__ inline bool bytes_equal(const uint8_t* a, const uint8_t* b, int64_t len) {
+  int64_t i = 0;
+  if ((((uintptr_t)a ^ (uintptr_t)b) & 3) == 0) {
+    for (; i < len && (((uintptr_t)(a + i)) & 3); ++i)
+      if (a[i] != b[i]) return false;
+    for (; i + 4 <= len; i += 4)
+      if (*reinterpret_cast<const uint32_t*>(a + i) != *reinterpret_cast<const uint32_t*>(b + i)) return false;
+  }
+  for (; i < len; ++i)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+
+struct StringKeys {
+  const int64_t* offs;          // child_n + 1
+  const uint8_t* bytes;
+  int64_t nbytes;
+  const uint8_t* kvalid;
+  const int64_t* needle_offs;   // per row (n + 1), or null: a constant
+  const uint8_t* needle_bytes;  // constant: 4 copies, copy m at m * const_stride + m (address = m mod 4)
+  int64_t needle_nbytes;
+  const uint8_t* needle_valid;
+  int64_t const_len, const_stride;
+  struct Needle {
+    const uint8_t* p;
+    int64_t len;
+  };
+  __device__ bool load(int64_t r, Needle& nd) const {
+    if (!needle_offs) {
+      nd = Needle{needle_bytes, const_len};
+      return true;
+    }
+    const int64_t a = needle_offs[r], b = needle_offs[r + 1];
+    nd = Needle{needle_bytes + a, b - a};
+    return row_ok(needle_valid, r) && a >= 0 && b >= a && b <= needle_nbytes;
+  }
+  __device__ bool hit(int64_t c, const Needle& nd) const {
+    if (kvalid && !kvalid[c]) return false;
+    const int64_t a = offs[c], b = offs[c + 1];
+    if (b - a != nd.len || a < 0 || b > nbytes) return false;
+    const uint8_t* k = bytes + a;
+    const uint8_t* q = nd.p;
+    if (!needle_offs) {           // the copy that shares this key's alignment: dword compares throughout
+      const int64_t m = (int64_t)((uintptr_t)k & 3);
+      q += m * const_stride + m;
+    }
+    return bytes_equal(k, q, nd.len);
+  }
+};
+
+template <class Keys>
+struct MapLookup {
+  const int64_t* se;
+  const uint8_t* valid;
+  int64_t n, child_n;
+  Keys keys;
+  int64_t* out;
+  // entries of the row that lie inside the child
+  __device__ void range(int64_t r, int64_t& st, int64_t& ln) const {
+    row_range(se, valid, r, st, ln);
+    if (st >= child_n) ln = 0;
+    else if (ln > child_n - st) ln = child_n - st;
+  }
+  __device__ int64_t work(int64_t r) const {
+    int64_t st, ln;
+    range(r, st, ln);
+    return ln;
+  }
+  __device__ void short_row(int64_t r) const {
+    int64_t st, ln, res = -1;
+    range(r, st, ln);
+    typename Keys::Needle nd;
+    if (keys.load(r, nd))
+      for (int64_t t = 0; t < ln; ++t)
+        if (keys.hit(st + t, nd)) {
+          res = st + t;
+          break;
+        }
+    out[r] = res;
+  }
+  __device__ void long_row(int64_t r, int lane) const {
+    int64_t st, ln, res = -1;
+    range(r, st, ln);
+    typename Keys::Needle nd;
+    const bool ok = keys.load(r, nd);   // wave-uniform: one row
+    for (int64_t base = 0; ok && base < ln && res < 0; base += kWave) {
+      const int64_t t = base + lane;
+      const uint64_t hb = __ballot(t < ln && keys.hit(st + t, nd));
+      if (hb) res = st + base + __ffsll((unsigned long long)hb) - 1;
+    }
+    if (lane == 0) out[r] = res;
+  }
+};
+
+template <class Keys>
+__global__ __launch_bounds__(kBlock) void map_lookup_kernel(MapLookup<Keys> f) { for_wave_tiles(f.n, kWave, f); }
+
 inline unsigned tile_grid(int64_t n) { return grid_for(n, kBlock, 1 << 16); }
 
 }  // namespace
@@ -788,6 +918,46 @@ void list_sort_idx(const int64_t* se, const uint8_t* valid, const int64_t* keys,
   SortOp f{se, valid, keys, kvalid, child_n, desc != 0, nulls_first != 0, n, offs, cap, idx, nullptr, nullptr};
   hipLaunchKernelGGL(list_sort_kernel, dim3(tile_grid(n)), dim3(kBlock), 0, s, f);
   check_launch("list_sort_idx", s);
+}
+
+template <class K>
+static void map_lookup_fixed(const int64_t* se, const uint8_t* valid, int64_t n, int64_t child_n, const void* keys,
+                             const uint8_t* kvalid, const int64_t* needle, const uint8_t* needle_valid,
+                             int64_t needle_const, int64_t* out, hipStream_t s) {
+  MapLookup<FixedKeys<K>> f{se, valid, n, child_n,
+                            FixedKeys<K>{static_cast<const K*>(keys), kvalid, needle, needle_valid, needle_const}, out};
+  hipLaunchKernelGGL(map_lookup_kernel<FixedKeys<K>>, dim3(tile_grid(n)), dim3(kBlock), 0, s, f);
+}
+
+void map_lookup_idx(const int64_t* se, const uint8_t* valid, int64_t n, int64_t child_n, int key_width,
+                    const void* keys, const uint8_t* kvalid, const int64_t* needle, const uint8_t* needle_valid,
+                    int64_t needle_const, int64_t* out, hipStream_t s) {
+  if (n == 0) return;
+  switch (key_width) {
+    case 1: map_lookup_fixed<int8_t>(se, valid, n, child_n, keys, kvalid, needle, needle_valid, needle_const, out, s); break;
+    case 2: map_lookup_fixed<int16_t>(se, valid, n, child_n, keys, kvalid, needle, needle_valid, needle_const, out, s); break;
+    case 4: map_lookup_fixed<int32_t>(se, valid, n, child_n, keys, kvalid, needle, needle_valid, needle_const, out, s); break;
+    case 8: map_lookup_fixed<int64_t>(se, valid, n, child_n, keys, kvalid, needle, needle_valid, needle_const, out, s); break;
+    default: throw std::invalid_argument("map_lookup_idx: key width");
+  }
+  check_launch("map_lookup_idx", s);
+}
+
+void map_lookup_idx_str(const int64_t* se, const uint8_t* valid, int64_t n, int64_t child_n, const int64_t* key_offs,
+                        const uint8_t* key_bytes, int64_t key_nbytes, const uint8_t* kvalid,
+                        const int64_t* needle_offs, const uint8_t* needle_bytes, int64_t needle_nbytes,
+                        const uint8_t* needle_valid, int64_t const_len, int64_t const_stride, int64_t* out,
+                        hipStream_t s) {
+  if (n == 0) return;
+  if (!needle_offs && (const_len < 0 || const_stride < const_len || (const_stride & 3) ||
+                       needle_nbytes < 4 * const_stride + 3 || ((uintptr_t)needle_bytes & 3)))
+    throw std::invalid_argument("map_lookup_idx_str: constant needle buffer");
+  MapLookup<StringKeys> f{se, valid, n, child_n,
+                          StringKeys{key_offs, key_bytes, key_nbytes, kvalid, needle_offs, needle_bytes, needle_nbytes,
+                                     needle_valid, const_len, const_stride},
+                          out};
+  hipLaunchKernelGGL(map_lookup_kernel<StringKeys>, dim3(tile_grid(n)), dim3(kBlock), 0, s, f);
+  check_launch("map_lookup_idx", s);
 }
 
 void list_element_idx(const int64_t* se, const uint8_t* valid, const int64_t* pos, const uint8_t* pos_valid,

@@ -140,7 +140,7 @@ std::vector<Token> tokenize(const std::string& t) {
       }
     }
     if (matched) continue;
-    if (std::string("+-*/%=<>(),.;~[]:").find(c) != std::string::npos) {
+    if (std::string("+-*/%=<>(),.;~[]:{}").find(c) != std::string::npos) {
       out.push_back({Token::Op, std::string(1, c), start});
       ++i;
       continue;
@@ -1002,6 +1002,20 @@ class Parser {
     return f;
   }
 
+  NodeP mapLiteral() {  // MAP {k1: v1, k2: v2} -> make_map(k1, v1, k2, v2)
+    expectOp("{");
+    auto f = make("func", "make_map");
+    if (!acceptOp("}")) {
+      do {
+        f->kids.push_back(expr());
+        expectOp(":");
+        f->kids.push_back(expr());
+      } while (acceptOp(","));
+      expectOp("}");
+    }
+    return f;
+  }
+
   NodeP lit(const std::string& type, const std::string& s) {
     auto n = make("lit", s);
     n->flags["type"] = type;
@@ -1146,6 +1160,7 @@ class Parser {
       case Token::QuotedIdent: {
         std::string name = next().text;
         if (name == "array" && t.kind == Token::Ident && isOp("[")) return arrayLiteral();
+        if (lower(name) == "map" && t.kind == Token::Ident && isOp("{")) return mapLiteral();
         if (isOp("(") && t.kind == Token::Ident) {
           if (name == "trim") return trimCall();
           if (name == "position") {  // POSITION(needle IN haystack) -> strpos(haystack, needle)

@@ -61,7 +61,7 @@ class Column:
 
     @property
     def nested(self) -> "Nested":
-        """LIST / STRUCT columns: the child column(s) the rows point into."""
+        """LIST / STRUCT / MAP columns: the child column(s) the rows point into."""
         assert self.dtype.is_nested and isinstance(self.dictionary, Nested), self
         return self.dictionary
 
@@ -162,6 +162,20 @@ class Column:
             child = Column.from_arrow(flat, device=device, dtype=dtype.child, dict_encode=False)
             data = torch.from_numpy(np.stack([starts, lens], axis=1).astype(np.int64)).to(device)
             return Column(dtype, data, valid, dictionary=Nested(child=child))
+        if dtype.kind == "map":
+            # (start, length) pairs straight from the offsets (arr.offsets honours a slice's offset);
+            # only the span of the children the rows reference is imported
+            off = np.asarray(arr.offsets.to_numpy(zero_copy_only=False), dtype=np.int64) if n else np.zeros(1, np.int64)
+            lo, hi = int(off[0]), int(off[-1])
+            starts, lens = off[:-1] - lo, off[1:] - off[:-1]
+            if valid is not None:
+                lens = np.where(arr.is_valid().to_numpy(zero_copy_only=False), lens, 0)
+            kids = {"key": Column.from_arrow(arr.keys.slice(lo, hi - lo), device=device, dtype=dtype.key,
+                                             dict_encode=False),
+                    "value": Column.from_arrow(arr.items.slice(lo, hi - lo), device=device, dtype=dtype.value,
+                                               dict_encode=False)}
+            data = torch.from_numpy(np.stack([starts, lens], axis=1).astype(np.int64)).to(device)
+            return Column(dtype, data, valid, dictionary=Nested(children=kids))
         if dtype.kind == "struct":
             kids = {}
             for i, (fname, ft) in enumerate(dtype.fields):
@@ -270,7 +284,8 @@ class Column:
 
 
 class Nested:
-    """Child column(s) of a LIST (``child``) or STRUCT (``children``) column,
+    """Child column(s) of a LIST (``child``), STRUCT (``children`` by field
+    name) or MAP (``children`` "key" and "value", equally long) column,
     carried in ``Column.dictionary`` so every operator that moves rows keeps
     them (rows are views: (start, length) pairs or row ids into the child)."""
 
@@ -313,6 +328,14 @@ def _nested_to_arrow(col: "Column", n: int, validity) -> pa.Array:
     off = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     idx = (np.repeat(starts - off[:-1], lens) + np.arange(off[-1], dtype=np.int64)) if off[-1] else np.zeros(0, np.int64)
+    if dt.kind == "map":
+        take_idx = pa.array(idx, pa.int64())
+        kids = []
+        for name, ft in dt.fields:
+            ch = col.nested.children[name].to_arrow()
+            kids.append((pc.take(ch, take_idx) if len(idx) else pa.array([], ft.to_arrow())).cast(ft.to_arrow()))
+        return pa.MapArray.from_arrays(pa.array(off.astype(np.int32)), kids[0], kids[1],
+                                       mask=pa.array(mask) if mask is not None else None)
     child = col.nested.child.to_arrow()
     vals = pc.take(child, pa.array(idx, pa.int64())) if len(idx) else pa.array([], dt.child.to_arrow())
     vals = vals.cast(dt.child.to_arrow())

@@ -47,7 +47,9 @@ _LIST_FAMILY = ("array_slice", "array_pop_front", "array_pop_back", "array_empty
                 "array_positions", "array_has_expr", "array_has_all", "array_has_any", "array_remove",
                 "array_replace", "array_max", "array_min", "array_distinct", "array_union", "array_intersect",
                 "array_except", "array_sort", "list_cast")
-_NESTED = _NESTED + _LIST_FAMILY
+#: the MAP family (ops/nested.py): views over the key / value children, the lookup kernel, construction
+_MAP_FAMILY = ("make_map", "map_from_lists", "map_keys", "map_values", "map_entries", "map_element", "map_extract")
+_NESTED = _NESTED + _LIST_FAMILY + _MAP_FAMILY
 
 
 class Scalar:
@@ -671,7 +673,22 @@ class Evaluator:
             raise ExecutionError("unnest() is only valid as a SELECT list item or in FROM")
         if name in _LIST_FAMILY:
             return self._list_family(e, [col(i) for i in range(len(args))])
+        if name in _MAP_FAMILY:
+            return self._map_family(e, [col(i) for i in range(len(args))], n, dev)
         raise NotSupported(f"function {name}")
+
+    def _map_family(self, e: Func, c, n: int, dev) -> Value:
+        from ..ops import nested as NS
+        name = e.name
+        if name == "make_map":
+            return NS.make_map(c[0::2], c[1::2], n, e.dtype, dev)
+        if name == "map_from_lists":
+            return NS.map_from_lists(c[0], c[1], e.dtype)
+        if name in ("map_element", "map_extract"):
+            fn = NS.map_element if name == "map_element" else NS.map_extract
+            # a constant key stays a constant (e.options), a key expression is one needle per row
+            return fn(c[0], c[1], False) if len(c) > 1 else fn(c[0], e.options[0], True)
+        return {"map_keys": NS.map_keys, "map_values": NS.map_values, "map_entries": NS.map_entries}[name](c[0])
 
     def _list_family(self, e: Func, c) -> Value:
         from ..columnar import Nested
@@ -715,7 +732,7 @@ class Evaluator:
             return Scalar(list(vals), e.dtype)
         if name == "struct":
             return Scalar(dict(zip(e.options, vals)), e.dtype)
-        if any(v is None for v in vals) and name not in _LIST_FAMILY:   # the list family has its own NULL rules
+        if any(v is None for v in vals) and name not in _LIST_FAMILY + _MAP_FAMILY:   # own NULL rules
             return Scalar(None, e.dtype)
         if name == "upper":
             return Scalar(vals[0].upper(), T.UTF8)

@@ -1,5 +1,5 @@
-"""LIST / STRUCT column operations (csrc/kernels/nested.hip + the gather and
-range-expansion kernels).
+"""LIST / STRUCT / MAP column operations (csrc/kernels/nested.hip + the gather
+and range-expansion kernels).
 
 Parity: DataFusion's nested functions (reference Cargo.lock:1125
 datafusion-functions-nested: make_array / ``[..]`` literals, array_length,
@@ -9,9 +9,13 @@ named_struct / get_field), reached through ``SessionContext::sql``
 
 Layout (types.py): a LIST row is an (start, length) int64 pair into
 ``col.nested.child``; a STRUCT row is an int64 row id into each of
-``col.nested.children``. Row movement (filters, joins, sorts) therefore
-gathers 16 / 8 bytes per row and never touches the children; functions turn
-into index arithmetic plus one child gather.
+``col.nested.children``; a MAP row is the LIST's (start, length) pair over
+two equally long children, ``col.nested.children["key"]`` and ``["value"]``
+(entry t of row r is child row start + t in both), so map_keys / map_values
+are LIST views sharing ``data`` and cardinality is ``data[:, 1]``. Row
+movement (filters, joins, sorts) therefore gathers 16 / 8 bytes per row and
+never touches the children; functions turn into index arithmetic plus one
+child gather.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ from .. import types as T
 from ..columnar import Column, Nested
 from ..utils.errors import ExecutionError, NotSupported
 from ._lib import KERNEL_CALLS
-from ._lib import is_gpu, launch, ptr, stream, to_host_int
+from ._lib import check_not_capturing, is_gpu, launch, ptr, stream, to_host_int
 
 
 def _cat_children(children: List[Column]) -> Column:
@@ -47,6 +51,16 @@ def concat(cols: Sequence[Column], valid: Optional[torch.Tensor]) -> Column:
             base += len(ch)
         return Column(dt, torch.cat(datas), valid, dictionary=Nested(child=_cat_children(kids)))
     kids: Dict[str, List[Column]] = {n: [] for n, _ in dt.fields}
+    if dt.kind == "map":
+        for c in cols:
+            d = c.data.clone()
+            d[:, 0] += base
+            datas.append(d)
+            for n in kids:
+                kids[n].append(c.nested.children[n])
+            base += len(c.nested)
+        return Column(dt, torch.cat(datas), valid,
+                      dictionary=Nested(children={n: _cat_children(v) for n, v in kids.items()}))
     for c in cols:
         datas.append(c.data + base)
         for n, _ in dt.fields:
@@ -800,3 +814,248 @@ def sort(col: Column, desc: bool = False, nulls_first: bool = True) -> Column:
         perm = argsort([(p, False, False, None), (keys.index_select(0, c), desc, nulls_first, ev)], total, dev)
         idx = c.index_select(0, perm.long())
     return _list_col(col.dtype, _se_from(off), col.valid, take(child, idx, neg=True))
+
+
+# ======================================================================= map functions
+# DataFusion's map family (datafusion-functions-nested) on the MAP layout. The
+# reference carries no fixtures for these, so the semantics are fixed here:
+#   * every function gives NULL for a NULL map row;
+#   * map_keys / map_values / map_entries are views over the children (entry
+#     order kept), cardinality is the row's length;
+#   * m[k] / element_at(m, k) is the value of the FIRST entry (in entry order)
+#     whose key equals k, NULL when none does; map_extract(m, k) is that value
+#     as a one-element list, [NULL] when none does (DataFusion's behaviour,
+#     not its documented "empty list");
+#   * a NULL needle never matches (keys cannot be NULL): m[k] is NULL and
+#     map_extract gives [NULL];
+#   * make_map / MAP {..} / map(keys, values) validate when the statement
+#     runs: a NULL key ("map key cannot be null"), two equal keys in one row
+#     ("map key must be unique") and map() lists of different lengths are
+#     ExecutionErrors; map() of a NULL list is NULL;
+#   * imported Arrow maps are taken as they are (duplicate keys included).
+
+#: key types a lookup or a construction accepts (the binder answers NotSupported for the rest)
+def map_key_ok(t: T.DataType) -> bool:
+    return t.is_integer or t.kind in ("bool", "date32", "timestamp", "utf8") or \
+        (t.is_decimal and t.precision <= 18)
+
+
+def _map_col(dtype: T.DataType, se: torch.Tensor, valid, keys: Column, values: Column) -> Column:
+    return Column(dtype, se, valid, dictionary=Nested(children={"key": keys, "value": values}))
+
+
+def map_keys(col: Column) -> Column:
+    """map_keys(m): List(key), a view sharing the map's (start, length) rows."""
+    return _list_col(T.LIST(col.dtype.key), col.data, col.valid, col.nested.children["key"])
+
+
+def map_values(col: Column) -> Column:
+    """map_values(m): List(value), a view like map_keys."""
+    return _list_col(T.LIST(col.dtype.value), col.data, col.valid, col.nested.children["value"])
+
+
+def map_entries(col: Column) -> Column:
+    """map_entries(m): List(Struct(key, value)); the struct child is row ids
+    over the map's own children."""
+    kids = col.nested.children
+    st = T.STRUCT(list(col.dtype.fields))
+    child = Column(st, _rowids(len(col.nested), col.device), None, dictionary=Nested(children=dict(kids)))
+    return _list_col(T.LIST(st), col.data, col.valid, child)
+
+
+def _needle_bytes(value: str, device) -> Tuple[torch.Tensor, int, int]:
+    """Device buffer of a constant string needle for map_lookup_idx_str: four
+    copies, copy m at byte m * stride + m, so a key at any byte alignment has
+    a copy it compares with dword by dword."""
+    from . import strings as S
+    b = value.encode("utf-8")
+    stride = (len(b) + 3) // 4 * 4 + 4
+
+    def build():
+        buf = bytearray(4 * stride + 4)
+        for m in range(4):
+            buf[m * stride + m: m * stride + m + len(b)] = b
+        return torch.frombuffer(buf, dtype=torch.uint8).clone().to(device)
+    return S._consts(("map_needle", b, str(device)), build), len(b), stride
+
+
+def _dict_code(col: Column, value: str) -> int:
+    """Code of ``value`` in a dictionary column's dictionary (-1: absent),
+    found once per dictionary and needle."""
+    cache = col.dictionary.derived()
+    key = ("code_of", value)
+    if key not in cache:
+        check_not_capturing("dictionary code lookup")
+        vals = col.dict_values()
+        cache[key] = vals.index(value) if value in vals else -1
+    return cache[key]
+
+
+def _lookup_by_position(col: Column, needle: Column) -> torch.Tensor:
+    """Child row of the first match through the list equality keys
+    (array_position): per-row needles against a dictionary-coded key child,
+    and the CPU form of per-row string needles."""
+    pos = position(map_keys(col), needle)
+    ok = pos.valid if pos.valid is not None else torch.ones_like(pos.data, dtype=torch.bool)
+    return torch.where(ok, _starts(col) + pos.data - 1, torch.full_like(pos.data, -1))
+
+
+def map_lookup_idx(col: Column, needle, needle_is_const: bool) -> torch.Tensor:
+    """Per row the child row of the first entry whose key equals the needle,
+    -1 for none (no match, NULL map row, NULL needle). ``needle``: a constant
+    in the engine's representation of the key type (None never matches) or a
+    Column of the key type with one needle per row. Keys are read in place:
+    fixed-width keys at their own width, plain strings by length and bytes, a
+    dictionary-coded key child through its codes once the constant's code is
+    known; only per-row needles over a dictionary-coded key child go through
+    the list equality keys."""
+    from . import strings as S
+    n = len(col)
+    dev = col.device
+    kc = col.nested.children["key"]
+    if needle_is_const and needle is None or n == 0:
+        return torch.full((n,), -1, dtype=torch.int64, device=dev)
+    nv = None if needle_is_const else needle.valid
+    if kc.dtype.is_string:
+        if needle_is_const and kc.is_dict:
+            code = _dict_code(kc, str(needle))
+            if code < 0:
+                return torch.full((n,), -1, dtype=torch.int64, device=dev)
+            keys, nconst, nt = kc.data, code, None
+        elif kc.is_dict:
+            return _lookup_by_position(col, needle)
+        else:
+            keys = None
+    else:
+        if kc.is_wide:
+            raise NotSupported("map lookup over 128-bit decimal keys")
+        keys = kc.data
+        nconst = 0 if not needle_is_const else int(needle)
+        nt = None if needle_is_const else needle.data.to(torch.int64).contiguous()
+    se = col.data.contiguous()
+    if is_gpu(se):
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        if keys is not None:
+            keys = keys.contiguous()
+            launch("map_lookup_idx").map_lookup_idx(ptr(se), ptr(col.valid), n, len(kc), keys.element_size(),
+                                                    ptr(keys), ptr(kc.valid), ptr(nt), ptr(nv), nconst, ptr(out),
+                                                    stream(out))
+            return out
+        koff, kb = kc.offsets.contiguous(), kc.data.contiguous()
+        if needle_is_const:
+            buf, ln, stride = _needle_bytes(str(needle), dev)
+            noff, nb = None, buf
+        else:
+            nd = S.decode(needle) if needle.is_dict else needle
+            noff, nb, ln, stride = nd.offsets.contiguous(), nd.data.contiguous(), 0, 0
+        launch("map_lookup_idx").map_lookup_idx_str(ptr(se), ptr(col.valid), n, len(kc), ptr(koff), ptr(kb),
+                                                    kb.numel(), ptr(kc.valid), ptr(noff), ptr(nb), nb.numel(),
+                                                    ptr(nv), ln, stride, ptr(out), stream(out))
+        return out
+    # CPU: the first matching element per row
+    if keys is None and not needle_is_const:
+        return _lookup_by_position(col, needle)
+    p, c, _, _ = _elements(map_keys(col))
+    if keys is None:
+        eq = S.in_list(kc, [str(needle)]).to(torch.bool).index_select(0, c)
+    elif nt is None:
+        eq = keys.index_select(0, c).to(torch.int64) == nconst
+    else:
+        eq = keys.index_select(0, c).to(torch.int64) == nt.index_select(0, p)
+        if nv is not None:
+            eq = eq & nv.index_select(0, p)
+    if kc.valid is not None:
+        eq = eq & kc.valid.index_select(0, c)
+    idx = torch.full((n,), _I64_MAX, dtype=torch.int64).scatter_reduce(
+        0, p, torch.where(eq, c, torch.full_like(c, _I64_MAX)), reduce="amin")
+    return torch.where(idx == _I64_MAX, torch.full_like(idx, -1), idx)
+
+
+def map_element(col: Column, needle, needle_is_const: bool) -> Column:
+    """m[k] / element_at(m, k): the value, NULL when the key is absent."""
+    from .gather import take
+    return take(col.nested.children["value"], map_lookup_idx(col, needle, needle_is_const), neg=True)
+
+
+def map_extract(col: Column, needle, needle_is_const: bool) -> Column:
+    """map_extract(m, k): [value] of the first matching entry, [NULL] when
+    none matches, NULL for a NULL map."""
+    from .gather import take
+    n = len(col)
+    child = take(col.nested.children["value"], map_lookup_idx(col, needle, needle_is_const), neg=True)
+    if is_gpu(col.data) and n:
+        se = torch.empty((n, 2), dtype=torch.int64, device=col.device)
+        launch("list_slots").list_slots(n, 1, ptr(se), stream(se))
+    else:
+        r = _rowids(n, col.device)
+        se = torch.stack([r, torch.ones_like(r)], 1)
+    return _list_col(T.LIST(col.dtype.value), se, col.valid, child)
+
+
+def _check_map_keys(keys: Column, mismatch: Optional[torch.Tensor] = None) -> None:
+    """Construction errors of a map whose keys are the rows of the list
+    column ``keys`` (its child holds exactly the entries): a NULL key, two
+    equal keys in one row (the distinct keys of a row, counted by the set
+    kernels over the list equality keys, against its length) and, for map(),
+    rows whose two lists differ in length. One readback for all of them."""
+    from ._lib import to_host_ints
+    n = len(keys)
+    if n == 0:
+        return
+    dev = keys.device
+    kc = keys.nested.child
+    ln = _vlen(keys)
+    flag = lambda t: t.any().reshape(1).to(torch.int64)   # noqa: E731
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    f_len = flag(mismatch) if mismatch is not None else zero
+    f_null = flag(~kc.valid) if kc.valid is not None and len(kc) else zero
+    k, kv = _eq_keys(kc)
+    cnt = None
+    if is_gpu(k):
+        cnt = torch.empty(n, dtype=torch.int64, device=dev)
+        launch("list_set_count").list_set_count(ptr(keys.data.contiguous()), ptr(keys.valid), ptr(k), ptr(kv),
+                                                k.numel(), 0, 0, 0, 0, 0, _SET_OPS["distinct"], n, ptr(cnt),
+                                                stream(cnt))
+        bad_len, bad_null, bad_dup, longest = to_host_ints(torch.cat([f_len, f_null, flag(cnt != ln),
+                                                                      ln.max().reshape(1)]))
+        if longest > min(LIST_FAST_MAX, launch_bound()):
+            cnt = None
+    if cnt is None:
+        if is_gpu(k):
+            KERNEL_CALLS["list_set_generic"] += 1
+        off, _ = _set_generic("distinct", keys, None, kc, k, kv, len(kc))
+        bad_len, bad_null, bad_dup = to_host_ints(torch.cat([f_len, f_null, flag((off[1:] - off[:-1]) != ln)]))
+    if bad_len:
+        raise ExecutionError("map(): the key list and the value list of a row differ in length")
+    if bad_null:
+        raise ExecutionError("map key cannot be null")
+    if bad_dup:
+        raise ExecutionError("map key must be unique")
+
+
+def make_map(key_cols: Sequence[Column], value_cols: Sequence[Column], n: int, dtype: T.DataType, device) -> Column:
+    """make_map(k1, v1, ..) / MAP {k1: v1, ..}: one map of len(key_cols)
+    entries per row, keys and values interleaved like make_array."""
+    keys = make_list(key_cols, n, T.LIST(dtype.key), device)
+    vals = make_list(value_cols, n, T.LIST(dtype.value), device)
+    if key_cols:
+        _check_map_keys(keys)
+    return _map_col(dtype, keys.data, None, keys.nested.child, vals.nested.child)
+
+
+def map_from_lists(keys: Column, vals: Column, dtype: T.DataType) -> Column:
+    """map(keys_list, values_list): the two lists zipped per row, NULL when
+    either is NULL. Both lists are compacted into one entry order (the
+    list_parts kernels), whatever their children looked like."""
+    n = len(keys)
+    valid = _and(keys.valid, vals.valid)
+    lk, lv = lengths(keys).clamp(min=0), lengths(vals).clamp(min=0)
+    mismatch = lk != lv
+    ln = torch.minimum(lk, lv)
+    if valid is not None:
+        mismatch = mismatch & valid
+        ln = torch.where(valid, ln, torch.zeros_like(ln))
+    k2 = _from_parts([(_starts(keys), ln, 1)], keys.nested.child, T.LIST(dtype.key), valid, n)
+    v2 = _from_parts([(_starts(vals), ln, 1)], vals.nested.child, T.LIST(dtype.value), valid, n)
+    _check_map_keys(k2, mismatch)
+    return _map_col(dtype, k2.data, valid, k2.nested.child, v2.nested.child)

@@ -233,6 +233,7 @@ class Binder:
         return on
 
     def _distinct(self, plan: Plan) -> Plan:
+        _no_map_keys(plan.schema, "DISTINCT")
         groups = [(ColInfo(self.ids(), c.name, c.dtype, c.nullable), c.ref()) for c in plan.schema]
         return Aggregate(plan, groups, [])
 
@@ -262,6 +263,7 @@ class Binder:
             asc = not o.get("desc")
             nf = o.get("nulls", "last" if asc else "first") == "first"
             keys.append((bound, asc, nf))
+        _no_map_keys([k for k, _, _ in keys], "ORDER BY")
         return BoundQuery(Sort(bq.plan, keys), bq.names)
 
     # ================================================================== select
@@ -436,6 +438,7 @@ class Binder:
         if distinct:
             plan = self._distinct_keep(plan)
         if sort_keys:
+            _no_map_keys([k for k, _, _ in sort_keys], "ORDER BY")
             plan = Sort(plan, sort_keys)
             if hidden:
                 plan = Project(plan, [(c, c.ref()) for c, _ in proj])
@@ -462,6 +465,7 @@ class Binder:
     def _distinct_keep(self, plan: Project) -> Plan:
         # DISTINCT keeps the projected cids so ORDER BY references stay valid
         groups = [(c, c.ref()) for c in plan.schema]
+        _no_map_keys(plan.schema, "DISTINCT")
         return Aggregate(plan, [(ColInfo(c.cid, c.name, c.dtype, c.nullable), _Passthrough(c)) for c, _ in groups], [])
 
     def _aggregate(self, plan: Plan, group_exprs: List[Expr], exprs: List[Expr], sets=None):
@@ -472,6 +476,7 @@ class Binder:
         ``grouping(...)`` reads."""
         groups: List[Tuple[ColInfo, Expr]] = []
         gmap: Dict[str, ColRef] = {}
+        _no_map_keys(group_exprs, "GROUP BY")
         for g in group_exprs:
             key = TPL.eq_sql(g)
             if key in gmap:
@@ -911,6 +916,7 @@ class Binder:
 
     def _cmp(self, op: str, l: Expr, r: Expr) -> Expr:
         lt, rt = l.dtype, r.dtype
+        _no_map_keys([l, r], f"comparison ({op})")
         # literal coercion towards the column type
         if lt != rt:
             if isinstance(r, Lit) and not isinstance(l, Lit):
@@ -1227,6 +1233,8 @@ class Binder:
                     t = a.dtype if t is None else (t if t == a.dtype else T.common_numeric(t, a.dtype))
             t = t or INT64
             return Func("make_array", [self._coerce(a, t) for a in args], T.LIST(t))
+        if name in _MAP_FUNCS or (name in ("cardinality", "array_element") and args and args[0].dtype.kind == "map"):
+            return self._map_func(name, args)
         if name in ("array_length", "cardinality", "list_length", "array_size"):
             a = need_list()
             return Func("array_length", [a], INT64)
@@ -1258,8 +1266,7 @@ class Binder:
         if name in _LIST_FAMILY or (name in ("array_has", "array_contains", "list_has", "list_contains")
                                     and len(args) == 2 and not isinstance(args[1], Lit)):
             return self._list_func(_LIST_FAMILY.get(name, "array_has"), name, args)
-        if name in ("array_dims", "list_dims", "string_to_array", "string_to_list", "map", "make_map", "map_keys",
-                    "map_values", "map_extract", "map_entries", "element_at"):
+        if name in ("array_dims", "list_dims", "string_to_array", "string_to_list"):
             raise NotSupported(f"function {name}() (outside the supported list function family)")
         if name in ("array_has", "array_contains", "list_has", "list_contains"):
             a = need_list()
@@ -1284,6 +1291,96 @@ class Binder:
             flags = lit(2, "flags", str) if len(args) > 2 else ""
             return Func("regexp_match", [a], T.LIST(UTF8), (pat, flags))
         raise NotSupported(f"function {name}()")
+
+    def _map_func(self, name: str, args: List[Expr]) -> Expr:
+        """The MAP family over the (start, length) layout with a key and a
+        value child (ops/nested.py). Keys: integers, bool, date, timestamp,
+        decimals of at most 18 digits and Utf8."""
+        from ..ops.nested import map_key_ok
+
+        def key_type(t):
+            if not map_key_ok(t):
+                raise NotSupported(f"{name}(): map keys of type {t}")
+            return t
+
+        def unify(types, what):
+            t = None
+            for x in types:
+                if x.kind == "null":
+                    continue
+                if t is None or t == x:
+                    t = x
+                elif t.is_numeric and x.is_numeric:
+                    t = T.common_numeric(t, x)
+                elif t.kind == "list" and x.kind == "list":
+                    t = T.common_numeric(t, x)
+                else:
+                    raise PlanError(f"{name}(): cannot combine {what} of types {t} and {x}")
+            return t or INT64
+
+        def as_list(e, ct):
+            if e.dtype.child == ct:
+                return e
+            if isinstance(e, Lit) and e.value is None:
+                return Lit(None, T.LIST(ct))
+            if e.dtype.child.kind == "null" and isinstance(e, Func) and e.name == "make_array":
+                return Func("make_array", [self._coerce(a, ct) for a in e.args], T.LIST(ct))
+            return Func("list_cast", [e], T.LIST(ct))
+        if name == "make_map":
+            if len(args) % 2:
+                raise PlanError("make_map() takes key, value pairs")
+            kt = key_type(unify([a.dtype for a in args[0::2]], "keys"))
+            vt = unify([a.dtype for a in args[1::2]], "values")
+            out = []
+            for k, v in zip(args[0::2], args[1::2]):
+                out += [self._coerce(k, kt), self._coerce(v, vt)]
+            return Func("make_map", out, T.MAP(kt, vt))
+        if name == "map":
+            if len(args) != 2 or any(a.dtype.kind not in ("list", "null") for a in args):
+                raise PlanError("map() takes a list of keys and a list of values "
+                                "(make_map(k1, v1, ..) takes pairs)")
+            args = [Lit(None, T.LIST(T.NULL)) if a.dtype.kind == "null" else a for a in args]
+            kt = key_type(args[0].dtype.child if args[0].dtype.child.kind != "null" else INT64)
+            vt = args[1].dtype.child if args[1].dtype.child.kind != "null" else INT64
+            return Func("map_from_lists", [as_list(args[0], kt), as_list(args[1], vt)], T.MAP(kt, vt))
+        if not args or args[0].dtype.kind != "map":
+            if name == "element_at" and args and args[0].dtype.kind == "list":
+                return self._nested_func("array_element", args)
+            raise NotSupported(f"{name}() needs a map argument, got {args[0].dtype if args else 'nothing'}")
+        m = args[0]
+        mt = m.dtype
+        if name == "cardinality":
+            _nargs(name, args, 1)
+            return Func("array_length", [m], INT64)
+        if name in ("map_keys", "map_values", "map_entries"):
+            _nargs(name, args, 1)
+            rt = {"map_keys": T.LIST(mt.key), "map_values": T.LIST(mt.value),
+                  "map_entries": T.LIST(T.STRUCT(list(mt.fields)))}[name]
+            return Func(name, [m], rt)
+        # lookups: m[k] / element_at(m, k) -> the value, map_extract(m, k) -> [value]
+        _nargs(name, args, 2)
+        kt = key_type(mt.key)
+        fn, rt = ("map_extract", T.LIST(mt.value)) if name == "map_extract" else ("map_element", mt.value)
+        k = args[1]
+        if isinstance(k, Lit):
+            if k.value is None:
+                return Func(fn, [m], rt, (None,))
+            if kt.is_integer and k.dtype.is_integer:
+                return Func(fn, [m], rt, (int(k.value),))       # compared as int64 against the key's own width
+            c = self._coerce_lit(k, kt)
+            v = c.value
+            if kt.is_decimal and c.dtype.is_decimal and c.dtype.scale != kt.scale:
+                # the key's scale: a constant with digits beyond it equals no key
+                f = 10 ** abs(c.dtype.scale - kt.scale)
+                v = v * f if c.dtype.scale < kt.scale else (v // f if v % f == 0 else None)
+            return Func(fn, [m], rt, (v,))
+        if kt.is_integer and k.dtype.is_integer:
+            return Func(fn, [m, self._coerce(k, INT64)], rt)
+        nt = k.dtype
+        if not (nt == kt or (kt.is_decimal and (nt.is_integer or (nt.is_decimal and nt.scale <= kt.scale)))
+                or (kt.is_temporal and nt.is_temporal)):
+            raise PlanError(f"{name}(): a key of type {nt} cannot be looked up in {mt}")
+        return Func(fn, [m, self._coerce(k, kt)], rt)
 
     def _list_func(self, fn: str, name: str, args: List[Expr]) -> Expr:
         """The array_* family over the (start, length) layout (ops/nested.py).
@@ -1809,6 +1906,7 @@ def _list_family() -> dict:
 
 
 _LIST_FAMILY = _list_family()
+_MAP_FUNCS = ("map", "make_map", "map_keys", "map_values", "map_entries", "map_extract", "element_at")
 _NESTED_FUNCS = _NESTED_FUNCS + tuple(_LIST_FAMILY)
 
 
@@ -1855,6 +1953,8 @@ def arrow_type_name(t: DataType) -> str:
                f"dict_is_ordered: false, metadata: {{}} }})"
     if k == "struct":
         return "Struct(" + ", ".join(f"{n} {arrow_type_name(ft)}" for n, ft in t.fields) + ")"
+    if k == "map":
+        return f"Map({arrow_type_name(t.key)}, {arrow_type_name(t.value)})"
     return str(t)
 
 
@@ -1986,6 +2086,13 @@ def _transform_top_down(e: Expr, fn) -> Expr:
     return e
 
 
+def _no_map_keys(xs, what: str) -> None:
+    """A MAP is no grouping, ordering, DISTINCT, join or comparison key."""
+    for x in xs:
+        if x.dtype.kind == "map":
+            raise NotSupported(f"{what} on a map ({x.dtype})")
+
+
 def _nargs(name, args, n):
     if len(args) != n:
         raise PlanError(f"{name}() takes {n} argument(s)")
@@ -2005,6 +2112,8 @@ _AGG_ALIASES = {"mean": "avg", "variance": "var_samp", "var": "var_samp", "var_p
 def _make_agg(name: str, arg: Optional[Expr], distinct: bool, flt, arg2: Optional[Expr] = None,
               param=None, order: Tuple = ()) -> AggCall:
     name = _AGG_ALIASES.get(name, name)
+    if arg is not None and arg.dtype.kind == "map" and (distinct or name not in ("count", "array_agg")):
+        raise NotSupported(f"{name}({'DISTINCT ' if distinct else ''}..) over a map ({arg.dtype})")
     if name == "count":
         return AggCall("count", arg, distinct, INT64, flt)
     if name == "approx_distinct":

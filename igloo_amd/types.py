@@ -11,9 +11,13 @@ Device layout (Arrow-compatible in HBM):
 * LIST(t): an [n, 2] int64 (start, length) view per row into a child column
   of type t (so a row gather is one 16-byte gather and the child values never
   move until the result is built); STRUCT: an int64 row id per row into one
-  child column per field. The child columns ride in ``Column.dictionary``
-  (a ``columnar.Nested`` payload), which every operator already carries
-  along with the rows.
+  child column per field; MAP(k, v): the same [n, 2] (start, length) pairs
+  as a LIST over two equally long children, ``key`` and ``value`` (entry t of
+  row r is child row start + t in both), so map_keys / map_values are
+  zero-copy LIST views that share ``data``, cardinality is ``data[:, 1]`` and
+  row movement stays a 16-byte gather. The child columns ride in
+  ``Column.dictionary`` (a ``columnar.Nested`` payload), which every operator
+  already carries along with the rows.
 """
 from __future__ import annotations
 
@@ -35,11 +39,21 @@ class DataType:
     precision: int = 0
     scale: int = 0
     child: Optional["DataType"] = None     # LIST element type
-    fields: Tuple = ()                     # STRUCT ((name, DataType), ...)
+    fields: Tuple = ()                     # STRUCT ((name, DataType), ...); MAP (("key", k), ("value", v))
 
     @property
     def is_nested(self) -> bool:
-        return self.kind in ("list", "struct")
+        return self.kind in ("list", "struct", "map")
+
+    @property
+    def key(self) -> "DataType":
+        """MAP key type."""
+        return self.fields[0][1]
+
+    @property
+    def value(self) -> "DataType":
+        """MAP value type."""
+        return self.fields[1][1]
 
     # ---------------------------------------------------------------- predicates
     @property
@@ -77,6 +91,8 @@ class DataType:
             return pa.list_(self.child.to_arrow())
         if k == "struct":
             return pa.struct([pa.field(n, t.to_arrow()) for n, t in self.fields])
+        if k == "map":
+            return pa.map_(self.key.to_arrow(), self.value.to_arrow())
         if k == "decimal":
             return pa.decimal128(max(self.precision, 1), self.scale)
         if k == "utf8":
@@ -92,6 +108,8 @@ class DataType:
             return f"List({self.child})"
         if self.kind == "struct":
             return "Struct(" + ", ".join(f"{n} {t}" for n, t in self.fields) + ")"
+        if self.kind == "map":
+            return f"Map({self.key}, {self.value})"
         return _NAMES.get(self.kind, self.kind)
 
     __repr__ = __str__
@@ -122,6 +140,10 @@ def STRUCT(fields) -> DataType:
     return DataType("struct", fields=tuple((str(n), t) for n, t in fields))
 
 
+def MAP(key: DataType, value: DataType) -> DataType:
+    return DataType("map", fields=(("key", key), ("value", value)))
+
+
 _TORCH = {
     "bool": torch.bool,
     "int8": torch.int8,
@@ -137,6 +159,7 @@ _TORCH = {
     "null": torch.bool,
     "list": torch.int64,
     "struct": torch.int64,
+    "map": torch.int64,
 }
 _ARROW = {
     "bool": pa.bool_(),
@@ -169,6 +192,8 @@ def from_arrow_type(t: pa.DataType) -> DataType:
         return from_arrow_type(t.value_type)
     if pa.types.is_list(t) or pa.types.is_large_list(t) or pa.types.is_fixed_size_list(t):
         return LIST(from_arrow_type(t.value_type))
+    if pa.types.is_map(t):
+        return MAP(from_arrow_type(t.key_type), from_arrow_type(t.item_type))
     if pa.types.is_struct(t):
         return STRUCT([(t.field(i).name, from_arrow_type(t.field(i).type)) for i in range(t.num_fields)])
     if pa.types.is_boolean(t):
