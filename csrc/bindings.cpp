@@ -309,15 +309,32 @@ PYBIND11_MODULE(_native, m) {
   m.def("probe_hit_tiles", [](int64_t m_) { return kern::probe_hit_tiles(m_); });
   m.def("probe_hits", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
                          bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t bits, uint64_t bmask,
-                         bool negate, uintptr_t words, uintptr_t tile_counts, uintptr_t s) {
+                         bool negate, int64_t n_build, uintptr_t fold, uintptr_t words, uintptr_t tile_counts,
+                         uintptr_t s) {
     if (m_ > 0 && (!keys || !thead || !words || !tile_counts || (!direct && !tkeys)))
       throw std::runtime_error("probe_hits: null buffer");
     kern::probe_hits(P<const void>(keys), key64, P<const uint8_t>(valid), m_, P<const int64_t>(tkeys),
-                     P<const void>(thead), rid64, cap, kmin, direct, P<const uint32_t>(bits), bmask, negate,
-                     P<unsigned long long>(words), P<int64_t>(tile_counts), S(s));
+                     P<const void>(thead), rid64, cap, kmin, direct, P<const uint32_t>(bits), bmask, negate, n_build,
+                     P<const uint32_t>(fold), P<unsigned long long>(words), P<int64_t>(tile_counts), S(s));
   });
   m.def("set_probe_grid_cap", &kern::set_probe_grid_cap);
   m.def("set_probe_bits", &kern::set_probe_bits);
+  m.def("set_probe_stream_min_rows", &kern::set_probe_stream_min_rows);
+  m.def("set_probe_stream_max_fill", &kern::set_probe_stream_max_fill);
+  m.def("last_probe_kernel", []() { return std::string(kern::last_probe_kernel()); });
+  m.attr("kFoldMinRows") = kern::probe_fold_min_rows();
+  m.attr("kFoldWords") = kern::probe_fold_words();
+  m.def("probe_fold_needed", &kern::probe_fold_needed);
+  m.def("probe_fold_build", [](uintptr_t bits, int64_t cap, uintptr_t fold, uintptr_t s) {
+    if (!bits || !fold || cap <= 0) throw std::runtime_error("probe_fold_build: null buffer");
+    kern::probe_fold_build(P<const uint32_t>(bits), cap, P<uint32_t>(fold), S(s));
+  });
+  m.def("join_table_init", [](uintptr_t thead, bool rid64, int64_t cap, uintptr_t tkeys, uintptr_t bits, int64_t nbw,
+                              uintptr_t dups, uintptr_t s) {
+    if (!thead || !dups || cap <= 0 || (bits && nbw <= 0)) throw std::runtime_error("join_table_init: null buffer");
+    kern::join_table_init(P<void>(thead), rid64, cap, P<int64_t>(tkeys), P<uint32_t>(bits), nbw,
+                          P<unsigned long long>(dups), S(s));
+  });
   m.def("probe_write", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
                           bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t words, uintptr_t tile_off,
                           uintptr_t out_probe, bool out64, uintptr_t out_build, int64_t out_cap, uintptr_t s) {

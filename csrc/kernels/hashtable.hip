@@ -21,6 +21,9 @@
 #include "common.h"
 #include "kernels.h"
 
+#include <cmath>
+#include <cstdint>
+
 namespace igloo {
 namespace kern {
 
@@ -930,34 +933,135 @@ __global__ __launch_bounds__(kBlock) void probe_bits_kernel(const K* __restrict_
 
 // The same probe for large probe sides: the membership bitmap, folded
 // modulo 64 KiB (word i = OR of the bitmap's words i, i + 16K, ...), sits in
-// LDS, read by every workgroup once; a probe key whose folded bit is clear
-// is out without touching L2 (each global bitmap read moves a whole cache
-// line for 4 useful bytes), and only folded hits consult the exact bitmap
-// (none when the bitmap fits the fold: then the fold is exact). Workgroups of
-// 1024 lanes, two per CU, loop over the tiles.
+// LDS; a probe key whose folded bit is clear is out without touching L2 (each
+// global bitmap read moves a whole cache line for 4 useful bytes), and only
+// folded hits consult the exact bitmap (none when the bitmap fits the fold:
+// then the fold is exact). Workgroups of 1024 lanes, two per CU.
 constexpr int kFoldWords = 16384;
 constexpr int kFoldBlock = 1024;
 constexpr int kFoldWaves = kFoldBlock / kWave;
 constexpr int kFoldSteps = kHitTile / (kFoldBlock * kBitsRows);   // 2
+constexpr int kWaveRows = kWave * kBitsRows;                      // rows of one wave's step (256)
+constexpr int kWaveSteps = kHitTile / kWaveRows;                  // steps of a wave that owns a tile (32)
 
+// The fold of a bitmap wider than kFoldWords, computed once per table
+// (ops/hashing.py JoinTable keeps it): every probe workgroup copies these
+// 64 KiB instead of OR-ing the whole bitmap (up to 4 MiB) again.
+__global__ __launch_bounds__(kBlock) void probe_fold_build_kernel(const uint32_t* __restrict__ bits, int64_t nbw,
+                                                                 uint32_t* __restrict__ fold) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;   // grid: kFoldWords / kBlock
+  uint32_t v = 0;
+#pragma unroll 8
+  for (int64_t j = i; j < nbw; j += kFoldWords) v |= bits[j];
+  fold[i] = v;
+}
+
+// The fold into LDS with 16-byte loads: src is the bitmap itself where it
+// fits (nsrc words, zero-padded), else the pre-pass's kFoldWords words.
+__device__ inline void fold_to_lds(uint32_t* fold, const uint32_t* __restrict__ src, int nsrc) {
+#pragma unroll
+  for (int i = threadIdx.x * 4; i < kFoldWords; i += kFoldBlock * 4) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (i + 4 <= nsrc) {
+      v = *reinterpret_cast<const uint4*>(src + i);
+    } else {
+      if (i < nsrc) v.x = src[i];
+      if (i + 1 < nsrc) v.y = src[i + 1];
+      if (i + 2 < nsrc) v.z = src[i + 2];
+    }
+    *reinterpret_cast<uint4*>(fold + i) = v;
+  }
+}
+
+// k - kmin as an unsigned value: d < cap is the whole range test. int32 keys
+// whose table span lies inside int32 (NARROW: kmin >= -2^31, kmin + cap <= 2^31)
+// need 32 bits only: a key below kmin wraps to at least 2^32 - (2^31 + kmin) >= cap.
+template <typename K, bool NARROW> struct FoldDiff { using type = uint64_t; };
+template <> struct FoldDiff<int32_t, true> { using type = uint32_t; };
+
+// Hit bits of 4 rows (bit j: row j; rows past m are masked by the caller).
+// Every lookup is unconditional (the fold index is masked into range, the
+// bitmap index of a row that is already out reads word 0), so the four
+// bitmap loads of a step are in flight together (see probe_heads).
+template <typename K, bool NARROW>
+__device__ inline uint32_t fold_test4(const K (&k)[kBitsRows], uint32_t vb, typename FoldDiff<K, NARROW>::type kmin,
+                                      typename FoldDiff<K, NARROW>::type cap, const uint32_t* fold,
+                                      const uint32_t* __restrict__ bits, bool exact, bool negate) {
+  using D = typename FoldDiff<K, NARROW>::type;
+  D d[kBitsRows];
+  bool ok[kBitsRows];
+#pragma unroll
+  for (int j = 0; j < kBitsRows; ++j) {
+    d[j] = (D)k[j] - kmin;
+    const uint32_t f = fold[(uint32_t)(d[j] >> 5) & (kFoldWords - 1)] >> ((uint32_t)d[j] & 31);
+    ok[j] = ((vb >> (8 * j)) & 0xffu) != 0 && d[j] < cap && (f & 1u);
+  }
+  if (!exact) {
+    uint32_t w[kBitsRows];
+#pragma unroll
+    for (int j = 0; j < kBitsRows; ++j) w[j] = bits[ok[j] ? d[j] >> 5 : 0];
+#pragma unroll
+    for (int j = 0; j < kBitsRows; ++j) ok[j] = ok[j] && ((w[j] >> ((uint32_t)d[j] & 31)) & 1u);
+  }
+  uint32_t nib = 0;
+#pragma unroll
+  for (int j = 0; j < kBitsRows; ++j) nib |= (ok[j] != negate ? 1u : 0u) << j;
+  return nib;
+}
+
+// rows 4*lane .. 4*lane+3 of a wave's 256 are bits 4*(lane%16) .. +3 of word
+// lane/16: OR the 16 nibbles of each lane group together (every lane of the
+// group gets the word)
+__device__ inline unsigned long long nibbles_to_word(uint32_t nib, int lane) {
+  unsigned long long w = (unsigned long long)nib << (4 * (lane & 15));
+  w |= __shfl_xor(w, 1, kWave);
+  w |= __shfl_xor(w, 2, kWave);
+  w |= __shfl_xor(w, 4, kWave);
+  w |= __shfl_xor(w, 8, kWave);
+  return w;
+}
+
+// 4 rows from r0 on, rows past m masked out: keys, validity bytes (vb) and
+// the mask of rows below m
 template <typename K>
+__device__ inline uint32_t load4_guarded(const K* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t r0,
+                                         int64_t m, K (&k)[kBitsRows], uint32_t& vb) {
+  if (r0 + kBitsRows <= m) {
+    load4(keys + r0, k);
+    vb = valid ? *reinterpret_cast<const uint32_t*>(valid + r0) : 0x01010101u;
+    return 0xfu;
+  }
+  uint32_t in = 0;
+  vb = 0;
+#pragma unroll
+  for (int j = 0; j < kBitsRows; ++j) {
+    const bool here = r0 + j < m;
+    k[j] = here ? keys[r0 + j] : K(0);
+    if (here && (!valid || valid[r0 + j])) vb |= 1u << (8 * j);
+    in |= (here ? 1u : 0u) << j;
+  }
+  return in;
+}
+
+// Tile loop of the short probes (below kStreamMinRows there are fewer tiles
+// than the chip has waves): all 16 waves of a workgroup share each tile.
+template <typename K, bool NARROW>
 __global__ __launch_bounds__(kFoldBlock) void probe_fold_kernel(const K* __restrict__ keys,
                                                                const uint8_t* __restrict__ valid, int64_t m,
                                                                int64_t cap, int64_t kmin,
-                                                               const uint32_t* __restrict__ bits, bool negate,
+                                                               const uint32_t* __restrict__ bits,
+                                                               const uint32_t* __restrict__ fold_src, bool negate,
                                                                unsigned long long* __restrict__ words,
                                                                int64_t* __restrict__ tile_counts) {
-  __shared__ uint32_t fold[kFoldWords];
+  using D = typename FoldDiff<K, NARROW>::type;
+  __shared__ alignas(16) uint32_t fold[kFoldWords];
   __shared__ int64_t red[kFoldWaves];
   const int lane = lane_id(), wave = threadIdx.x / kWave;
   const int64_t nbw = (cap + 31) >> 5;
-  for (int i = threadIdx.x; i < kFoldWords; i += kFoldBlock) {
-    uint32_t v = 0;
-    for (int64_t j = i; j < nbw; j += kFoldWords) v |= bits[j];
-    fold[i] = v;
-  }
-  __syncthreads();
   const bool exact = nbw <= kFoldWords;
+  fold_to_lds(fold, exact ? bits : fold_src, exact ? (int)nbw : kFoldWords);
+  __syncthreads();
+  const D dmin = (D)kmin, dcap = (D)cap;
   const int64_t tiles = (m + kHitTile - 1) / kHitTile;
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     int64_t cnt = 0;
@@ -965,37 +1069,13 @@ __global__ __launch_bounds__(kFoldBlock) void probe_fold_kernel(const K* __restr
     for (int g = 0; g < kFoldSteps; ++g) {
       const int64_t r0 = t * kHitTile + (int64_t)g * (kFoldBlock * kBitsRows) + (int64_t)threadIdx.x * kBitsRows;
       K k[kBitsRows];
-      uint32_t vb = 0x01010101u;
-      if (r0 + kBitsRows <= m) {
-        load4(keys + r0, k);
-        if (valid) vb = *reinterpret_cast<const uint32_t*>(valid + r0);
-      } else {
-        vb = 0;
-#pragma unroll
-        for (int j = 0; j < kBitsRows; ++j) {
-          const bool in = r0 + j < m;
-          k[j] = in ? keys[r0 + j] : K(0);
-          if (in && (!valid || valid[r0 + j])) vb |= 1u << (8 * j);
-        }
-      }
-      uint32_t nib = 0;
-#pragma unroll
-      for (int j = 0; j < kBitsRows; ++j) {
-        const int64_t d = (int64_t)k[j] - kmin;
-        bool ok = ((vb >> (8 * j)) & 0xffu) != 0 && d >= 0 && d < cap;
-        if (ok) ok = (fold[(d >> 5) & (kFoldWords - 1)] >> (d & 31)) & 1u;
-        if (ok && !exact) ok = (bits[(uint64_t)d >> 5] >> (d & 31)) & 1u;
-        const bool hit = r0 + j < m && (ok != negate);
-        nib |= (hit ? 1u : 0u) << j;
-      }
+      uint32_t vb;
+      const uint32_t in = load4_guarded(keys, valid, r0, m, k, vb);
+      const uint32_t nib = fold_test4<K, NARROW>(k, vb, dmin, dcap, fold, bits, exact, negate) & in;
       cnt += __popc(nib);
-      unsigned long long w = (unsigned long long)nib << (4 * (lane & 15));
-      w |= __shfl_xor(w, 1, kWave);
-      w |= __shfl_xor(w, 2, kWave);
-      w |= __shfl_xor(w, 4, kWave);
-      w |= __shfl_xor(w, 8, kWave);
+      const unsigned long long w = nibbles_to_word(nib, lane);
       const int64_t wrow = t * kHitTile + (int64_t)g * (kFoldBlock * kBitsRows) +
-                           (int64_t)wave * (kWave * kBitsRows) + (int64_t)(lane >> 4) * kWave;
+                           (int64_t)wave * kWaveRows + (int64_t)(lane >> 4) * kWave;
       if ((lane & 15) == 0 && wrow < m)
         words[t * kHitWords + g * (kHitWords / kFoldSteps) + wave * kBitsRows + (lane >> 4)] = w;
     }
@@ -1011,6 +1091,142 @@ __global__ __launch_bounds__(kFoldBlock) void probe_fold_kernel(const K* __restr
   }
 }
 
+// The long probes: every wave owns whole tiles (tile t of wave w in
+// workgroup b: t = 16 b + w, then on by the number of waves launched), so
+// the tile count is one wave reduction and no workgroup barrier follows the
+// one behind the fold. A wave walks its tile in 32 steps of 256 rows and
+// keeps the key and validity loads of the next kDepth steps in flight while
+// it tests the current one -- across its tiles too: the last steps of a tile
+// already load the first ones of the wave's next tile.
+template <typename K> constexpr int kStreamDepth = sizeof(K) == 4 ? 4 : 2;
+
+template <typename K, bool VALID>
+__device__ inline void stream_load(const K* __restrict__ keys, const uint8_t* __restrict__ valid, int64_t r0,
+                                   K (&k)[kBitsRows], uint32_t& vb) {
+  load4(keys + r0, k);
+  if constexpr (VALID) vb = *reinterpret_cast<const uint32_t*>(valid + r0);
+  else vb = 0x01010101u;
+}
+
+template <typename K, bool NARROW, bool VALID>
+__global__ __launch_bounds__(kFoldBlock, 8) void probe_stream_kernel(const K* __restrict__ keys,
+                                                                 const uint8_t* __restrict__ valid, int64_t m,
+                                                                 int64_t cap, int64_t kmin,
+                                                                 const uint32_t* __restrict__ bits,
+                                                                 const uint32_t* __restrict__ fold_src, bool negate,
+                                                                 unsigned long long* __restrict__ words,
+                                                                 int64_t* __restrict__ tile_counts) {
+  using D = typename FoldDiff<K, NARROW>::type;
+  constexpr int kDepth = kStreamDepth<K>;
+  static_assert(kWaveSteps % kDepth == 0, "the step loop is unrolled by the depth");
+  __shared__ alignas(16) uint32_t fold[kFoldWords];
+  const int lane = lane_id(), wave = threadIdx.x / kWave;
+  const int64_t nbw = (cap + 31) >> 5;
+  const bool exact = nbw <= kFoldWords;
+  fold_to_lds(fold, exact ? bits : fold_src, exact ? (int)nbw : kFoldWords);
+  __syncthreads();
+  const D dmin = (D)kmin, dcap = (D)cap;
+  const int64_t tiles = (m + kHitTile - 1) / kHitTile;
+  const int64_t full = m / kHitTile;   // tiles [0, full) have all their rows
+  const int64_t stride = (int64_t)gridDim.x * kFoldWaves;
+  const int64_t lrow = (int64_t)lane * kBitsRows;
+  K kq[kDepth][kBitsRows];
+  uint32_t vq[kDepth];
+  int64_t t = (int64_t)blockIdx.x * kFoldWaves + wave;
+  if (t < full) {
+#pragma unroll
+    for (int j = 0; j < kDepth; ++j)
+      stream_load<K, VALID>(keys, valid, t * kHitTile + j * kWaveRows + lrow, kq[j], vq[j]);
+  }
+  for (; t < tiles; t += stride) {
+    int cnt = 0;
+    unsigned long long* wout = words + t * kHitWords + (lane >> 4);
+    if (t < full) {
+      const int64_t tn = t + stride;
+      const bool nfull = tn < full;
+      // the slot's refill: step s + kDepth of this tile, or of the wave's
+      // next full tile; with neither left, step s's rows once more (in
+      // bounds, never used)
+      auto refill = [&](int j, int s) {
+        int64_t pt = t;
+        int ps = s + kDepth;
+        if (ps >= kWaveSteps) {
+          if (nfull) {
+            pt = tn;
+            ps -= kWaveSteps;
+          } else {
+            ps = s;
+          }
+        }
+        stream_load<K, VALID>(keys, valid, pt * kHitTile + ps * kWaveRows + lrow, kq[j], vq[j]);
+      };
+      auto emit = [&](int s, uint32_t nib) {
+        cnt += __popc(nib);
+        const unsigned long long w = nibbles_to_word(nib, lane);
+        if ((lane & 15) == 0) wout[s * kBitsRows] = w;
+      };
+      for (int s0 = 0; s0 < kWaveSteps; s0 += kDepth) {
+#pragma unroll
+        for (int j = 0; j < kDepth; ++j) {
+          const uint32_t nib = fold_test4<K, NARROW>(kq[j], vq[j], dmin, dcap, fold, bits, exact, negate);
+          refill(j, s0 + j);
+          emit(s0 + j, nib);
+        }
+      }
+    } else {
+      // the probe's last tile, partly filled: guarded loads, no pipeline
+      for (int s = 0; s < kWaveSteps; ++s) {
+        const int64_t r0 = t * kHitTile + s * kWaveRows + lrow;
+        K k[kBitsRows];
+        uint32_t vb;
+        const uint32_t in = load4_guarded(keys, valid, r0, m, k, vb);
+        const uint32_t nib = fold_test4<K, NARROW>(k, vb, dmin, dcap, fold, bits, exact, negate) & in;
+        cnt += __popc(nib);
+        const unsigned long long w = nibbles_to_word(nib, lane);
+        if ((lane & 15) == 0 && t * kHitTile + s * kWaveRows + (int64_t)(lane >> 4) * kWave < m)
+          wout[s * kBitsRows] = w;
+      }
+    }
+    const int64_t total = wave_reduce_sum((int64_t)cnt);
+    if (lane == 0) tile_counts[t] = total;
+  }
+}
+
+// One launch for everything join_build expects initialised: thead = -1,
+// tkeys = kEmptyKey (hashed tables), bits = 0, dups = 0. A segment is an
+// array of 4-byte words whose fill repeats every 8 bytes (lo, hi): 16-byte
+// stores over its whole chunks, word stores for the up to three words left.
+struct FillSeg {
+  uint32_t* p;
+  int64_t words;
+  uint32_t lo, hi;
+};
+
+__global__ __launch_bounds__(kBlock) void join_table_init_kernel(FillSeg a, FillSeg b, FillSeg c,
+                                                                unsigned long long* __restrict__ dups) {
+  const int64_t na = a.words >> 2, nb = b.words >> 2, nc = c.words >> 2;
+  const int64_t total = na + nb + nc;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+    uint32_t* p = a.p;
+    uint32_t lo = a.lo, hi = a.hi;
+    int64_t j = i;
+    if (j >= na) {
+      j -= na;
+      p = b.p, lo = b.lo, hi = b.hi;
+      if (j >= nb) {
+        j -= nb;
+        p = c.p, lo = c.lo, hi = c.hi;
+      }
+    }
+    reinterpret_cast<uint4*>(p)[j] = make_uint4(lo, hi, lo, hi);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 3) {
+    const FillSeg s = threadIdx.x == 0 ? a : threadIdx.x == 1 ? b : c;
+    for (int64_t w = s.words & ~(int64_t)3; w < s.words; ++w) s.p[w] = (w & 1) ? s.hi : s.lo;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 3) *dups = 0ULL;
+}
+
 }  // namespace
 
 int64_t probe_hit_tiles(int64_t m) { return (m + kHitTile - 1) / kHitTile; }
@@ -1023,26 +1239,108 @@ void set_probe_grid_cap(int cap) { g_probe_grid_cap = cap > 0 ? cap : (1 << 16);
 // bitmap for large probe sides (scripts/bench_probe.py A/B)
 static int g_probe_bits = 2;
 void set_probe_bits(int mode) { g_probe_bits = mode; }
-constexpr int64_t kFoldMinRows = 1 << 22;   // below: the fold's build per workgroup does not pay
+constexpr int64_t kFoldMinRows = 1 << 22;   // below: copying the fold per workgroup does not pay
 constexpr int64_t kFoldGrid = 512;          // two 1024-lane workgroups (64 KiB LDS each) per CU
+int64_t probe_fold_min_rows() { return kFoldMinRows; }
+int probe_fold_words() { return kFoldWords; }
+
+// probe_stream_kernel takes the probes of which every wave of its grid owns
+// a tile or more (512 workgroups x 16 waves x 8192 rows = 64M rows) -- below,
+// the tile loop of probe_fold_kernel keeps the chip filled -- and whose fold
+// filters well. A bitmap wider than the fold ORs nbw / 16384 words into each
+// folded bit: with n build keys over cap slots about
+// 1 - (1 - n/cap)^(nbw/16384) of the folded bits are set, and every key that
+// passes the fold costs a bitmap read from L2 that the streaming loop hides
+// worse than the tile loop does. probe_hits alone on an MI355X, int32 keys,
+// half the rows masked, tile loop / streaming loop in ms:
+//   fill 0.07 (40K keys over 1M): 0.043 / 0.043 at 32M rows, 0.093 / 0.083
+//     at 64M, 0.768 / 0.705 at 600M (TPC-H Q21's probe)
+//   exact fold (40K over 500K):   0.079 / 0.072 at 64M, 0.646 / 0.622 at 600M
+//   fill 0.11: 0.769 / 0.751 at 600M    fill 0.15: 0.778 / 0.793
+//   fill 0.25: 0.832 / 0.941            fill 0.88 (1.1M over 20M): 1.526 / 1.818
+// probe_bits_kernel took 1.466 ms at fill 0.07 and 1.780 ms at fill 0.88 (600M
+// rows): behind the tile loop at every fill, so no fill hands a probe to it.
+constexpr int64_t kStreamMinRows = kFoldGrid * kFoldWaves * kHitTile;
+constexpr double kStreamMaxFill = 0.1;
+static int64_t g_stream_min_rows = kStreamMinRows;
+static double g_stream_max_fill = kStreamMaxFill;
+void set_probe_stream_min_rows(int64_t rows) { g_stream_min_rows = rows >= 0 ? rows : kStreamMinRows; }
+void set_probe_stream_max_fill(double fill) { g_stream_max_fill = fill >= 0 ? fill : kStreamMaxFill; }
+
+enum ProbeKernel { kProbeNone = 0, kProbeScalar, kProbeBits, kProbeFold, kProbeStream };
+static ProbeKernel g_last_probe = kProbeNone;
+const char* last_probe_kernel() {
+  static const char* const names[] = {"none", "hits", "bits", "fold", "stream"};
+  return names[g_last_probe];
+}
+
+// which kernel serves a probe of m rows; vec: a direct table with an exact
+// bitmap and buffers aligned for the vector loads
+static ProbeKernel probe_plan(bool vec, int64_t m, int64_t cap, int64_t n_build) {
+  if (!vec || g_probe_bits < 1) return kProbeScalar;
+  if (g_probe_bits < 2 || m < kFoldMinRows) return kProbeBits;
+  if (m < g_stream_min_rows) return kProbeFold;
+  const int64_t nbw = (cap + 31) >> 5;
+  if (nbw > kFoldWords) {
+    const double load = n_build < cap ? (double)n_build / (double)cap : 1.0;
+    if (1.0 - std::pow(1.0 - load, (double)nbw / kFoldWords) > g_stream_max_fill) return kProbeFold;
+  }
+  return kProbeStream;
+}
+
+bool probe_fold_needed(int64_t m, int64_t cap) {
+  return ((cap + 31) >> 5) > kFoldWords && probe_plan(true, m, cap, 0) >= kProbeFold;
+}
+
+void probe_fold_build(const uint32_t* bits, int64_t cap, uint32_t* fold, hipStream_t stream) {
+  hipLaunchKernelGGL(probe_fold_build_kernel, dim3(kFoldWords / kBlock), dim3(kBlock), 0, stream, bits,
+                     (cap + 31) >> 5, fold);
+  check_launch("probe_fold_build", stream);
+}
+
+template <typename K, bool NARROW>
+static void launch_fold(ProbeKernel plan, const void* keys, const uint8_t* valid, int64_t m, int64_t cap, int64_t kmin,
+                        const uint32_t* bits, const uint32_t* fold, bool negate, unsigned long long* words,
+                        int64_t* tile_counts, hipStream_t stream) {
+  const int64_t tiles = probe_hit_tiles(m);
+  const K* k = static_cast<const K*>(keys);
+  const dim3 bf(kFoldBlock);
+  if (plan == kProbeFold) {
+    const dim3 gf(grid_for(tiles, 1, kFoldGrid));
+    hipLaunchKernelGGL((probe_fold_kernel<K, NARROW>), gf, bf, 0, stream, k, valid, m, cap, kmin, bits, fold, negate,
+                       words, tile_counts);
+    return;
+  }
+  const dim3 gs(grid_for(tiles, kFoldWaves, kFoldGrid));
+  if (valid)
+    hipLaunchKernelGGL((probe_stream_kernel<K, NARROW, true>), gs, bf, 0, stream, k, valid, m, cap, kmin, bits, fold,
+                       negate, words, tile_counts);
+  else
+    hipLaunchKernelGGL((probe_stream_kernel<K, NARROW, false>), gs, bf, 0, stream, k, valid, m, cap, kmin, bits, fold,
+                       negate, words, tile_counts);
+}
 
 void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
                 const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const uint32_t* bits,
-                uint64_t bmask, bool negate, unsigned long long* words, int64_t* tile_counts, hipStream_t stream) {
+                uint64_t bmask, bool negate, int64_t n_build, const uint32_t* fold, unsigned long long* words,
+                int64_t* tile_counts, hipStream_t stream) {
   if (m == 0) return;
   const dim3 g(grid_for(probe_hit_tiles(m), 1, g_probe_grid_cap)), b(kBlock);
   const bool vec = direct && bits && (bmask & kExactBits) && ((uintptr_t)keys & 15) == 0 &&
                    ((uintptr_t)valid & 3) == 0;
-  if (vec && g_probe_bits >= 2 && m >= kFoldMinRows) {
-    const int64_t tiles = probe_hit_tiles(m);
-    const dim3 gf((unsigned)(tiles < kFoldGrid ? tiles : kFoldGrid)), bf(kFoldBlock);
+  ProbeKernel plan = probe_plan(vec, m, cap, n_build);
+  // (the fold kernels copy the bitmap, or its fold, with 16-byte loads)
+  if (plan >= kProbeFold && (((uintptr_t)bits | (uintptr_t)fold) & 15)) plan = kProbeBits;
+  if (plan >= kProbeFold) {
+    if (((cap + 31) >> 5) > kFoldWords && !fold)
+      throw std::runtime_error("probe_hits: a bitmap wider than the fold needs probe_fold_build's scratch");
     if (key64)
-      hipLaunchKernelGGL(probe_fold_kernel<int64_t>, gf, bf, 0, stream, static_cast<const int64_t*>(keys), valid, m,
-                         cap, kmin, bits, negate, words, tile_counts);
+      launch_fold<int64_t, false>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
+    else if (kmin >= INT32_MIN && cap < (1LL << 31) && kmin + cap <= (1LL << 31))
+      launch_fold<int32_t, true>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
     else
-      hipLaunchKernelGGL(probe_fold_kernel<int32_t>, gf, bf, 0, stream, static_cast<const int32_t*>(keys), valid, m,
-                         cap, kmin, bits, negate, words, tile_counts);
-  } else if (vec && g_probe_bits >= 1) {
+      launch_fold<int32_t, false>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
+  } else if (plan == kProbeBits) {
     if (key64)
       hipLaunchKernelGGL(probe_bits_kernel<int64_t>, g, b, 0, stream, static_cast<const int64_t*>(keys), valid, m, cap,
                          kmin, bits, negate, words, tile_counts);
@@ -1055,7 +1353,22 @@ void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, c
   else
     DISPATCH_KEY3(key64, direct, int32_t, probe_hits_kernel, g, b, 0, stream, keys, valid, m, tkeys,
                   (const int32_t*)thead, cap, kmin, bits, bmask, negate, words, tile_counts);
+  g_last_probe = plan;
   check_launch("probe_hits", stream);
+}
+
+void join_table_init(void* thead, bool rid64, int64_t cap, int64_t* tkeys, uint32_t* bits, int64_t nbw,
+                     unsigned long long* dups, hipStream_t stream) {
+  if ((((uintptr_t)thead | (uintptr_t)tkeys | (uintptr_t)bits) & 15) || ((uintptr_t)dups & 7))
+    throw std::runtime_error("join_table_init: buffers must be 16-byte aligned");
+  const FillSeg a{static_cast<uint32_t*>(thead), rid64 ? 2 * cap : cap, 0xffffffffu, 0xffffffffu};
+  const FillSeg k{reinterpret_cast<uint32_t*>(tkeys), tkeys ? 2 * cap : 0, (uint32_t)(uint64_t)kEmptyKey,
+                  (uint32_t)((uint64_t)kEmptyKey >> 32)};
+  const FillSeg z{bits, bits ? nbw : 0, 0u, 0u};
+  const int64_t chunks = (a.words >> 2) + (k.words >> 2) + (z.words >> 2);
+  hipLaunchKernelGGL(join_table_init_kernel, dim3(grid_for(chunks, kBlock, 2048)), dim3(kBlock), 0, stream, a, k, z,
+                     dups);
+  check_launch("join_table_init", stream);
 }
 
 template <typename R, typename O>

@@ -186,9 +186,25 @@ void join_probe(const void* keys, bool key64, const uint8_t* valid, int64_t m, c
 int64_t probe_hit_tiles(int64_t m);
 void set_probe_grid_cap(int cap);
 void set_probe_bits(int mode);
+// A/B knobs of the folded-bitmap probes (negative: back to the built-in value)
+void set_probe_stream_min_rows(int64_t rows);
+void set_probe_stream_max_fill(double fill);
+int64_t probe_fold_min_rows();
+int probe_fold_words();
+// "hits" / "bits" / "fold" / "stream": the kernel the last probe_hits launched ("none" before the first)
+const char* last_probe_kernel();
+// true when a probe of m rows against an exact bitmap over cap slots takes a fold kernel and the bitmap
+// is wider than the fold: probe_hits then needs probe_fold_build's probe_fold_words() words
+bool probe_fold_needed(int64_t m, int64_t cap);
+void probe_fold_build(const uint32_t* bits, int64_t cap, uint32_t* fold, hipStream_t stream);
 void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
                 const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const uint32_t* bits,
-                uint64_t bmask, bool negate, unsigned long long* words, int64_t* tile_counts, hipStream_t stream);
+                uint64_t bmask, bool negate, int64_t n_build, const uint32_t* fold, unsigned long long* words,
+                int64_t* tile_counts, hipStream_t stream);
+// thead[cap] = -1, tkeys[cap] = the empty key (null: a direct table), bits[nbw] = 0 (null: none), dups = 0
+// in one launch; the buffers are 16-byte aligned
+void join_table_init(void* thead, bool rid64, int64_t cap, int64_t* tkeys, uint32_t* bits, int64_t nbw,
+                     unsigned long long* dups, hipStream_t stream);
 void probe_write(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
                  const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const unsigned long long* words,
                  const int64_t* tile_off, void* out_probe, bool out64, void* out_build, int64_t out_cap,

@@ -234,25 +234,27 @@ class JoinTable:
         N = launch("join_build")
         self.cap = span if self.direct else _next_pow2(2 * n)
         # Bloom filter for selective probes: ~8 bits per key, at most 4 MB (L2-resident)
-        self.bits, self.bmask = None, 0
+        self.bits, self.bmask, self._fold = None, 0, None
         if self.direct and EXACT_BITMAP and span <= EXACT_BITMAP_MAX_SPAN:
             # exact membership bitmap over the key span (<= 4 MB, L2-resident):
             # no false positives (csrc/kernels/hashtable.hip kExactBits)
-            self.bits = torch.zeros((span + 31) // 32, dtype=torch.int32, device=self.device)
+            self.bits = torch.empty((span + 31) // 32, dtype=torch.int32, device=self.device)
             self.bmask = 1 << 63
         elif n <= BLOOM_MAX_KEYS:
             nbits = min(max(_next_pow2(8 * n), 1 << 15), 1 << 25)
-            self.bits = torch.zeros(nbits // 32, dtype=torch.int32, device=self.device)
+            self.bits = torch.empty(nbits // 32, dtype=torch.int32, device=self.device)
             self.bmask = nbits - 1
         # row ids: int32 below 2^31 build rows, int64 above
         self.rid = torch.int32 if n < INT32_MAX else torch.int64
         self.rid64 = self.rid == torch.int64
-        self.thead = torch.full((self.cap,), -1, dtype=self.rid, device=self.device)
-        self.tkeys = (torch.empty(1, dtype=torch.int64, device=self.device) if self.direct
-                      else torch.full((self.cap,), EMPTY_KEY, dtype=torch.int64, device=self.device))
-        dups = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.thead = torch.empty(self.cap, dtype=self.rid, device=self.device)
+        self.tkeys = torch.empty(1 if self.direct else self.cap, dtype=torch.int64, device=self.device)
+        dups = torch.empty(1, dtype=torch.int64, device=self.device)
         k64 = keys.dtype == torch.int64
         st = stream(keys)
+        # thead = -1, tkeys = EMPTY_KEY (hashed), bits = 0, dups = 0: one launch
+        N.join_table_init(ptr(self.thead), self.rid64, self.cap, 0 if self.direct else ptr(self.tkeys),
+                          ptr(self.bits), 0 if self.bits is None else self.bits.numel(), ptr(dups), st)
         N.join_build(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
                      self.kmin, self.direct, ptr(dups), ptr(self.bits), self.bmask, st)
         if known_unique and CHECK_KEY_TAGS and not capturing():
@@ -351,8 +353,9 @@ class JoinTable:
         words = torch.empty(tiles * 128, dtype=torch.int64, device=dev)
         tcount = torch.empty(tiles, dtype=torch.int64, device=dev)
         bits, bmask = self._bloom(m)
+        fold = self._fold_scratch(m, bits, bmask, st)
         N.probe_hits(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
-                     self.kmin, self.direct, bits, bmask, negate, ptr(words), ptr(tcount), st)
+                     self.kmin, self.direct, bits, bmask, negate, self.n, fold, ptr(words), ptr(tcount), st)
         if self._unique is None:
             # deferred duplicate count: read back with the hit total (one sync);
             # duplicate build keys leave the pairs to the multi-match probe
@@ -422,6 +425,18 @@ class JoinTable:
         if self.bits is not None and m >= BLOOM_MIN_RATIO * self.n:
             return ptr(self.bits), self.bmask
         return 0, 0
+
+    def _fold_scratch(self, m: int, bits: int, bmask: int, st: int) -> int:
+        """The exact bitmap folded to the 64 KiB that probe_hits' fold kernels
+        keep in LDS, for bitmaps wider than that: computed by the first probe
+        that takes one of them and kept with the table (0: not needed)."""
+        N = native()
+        if not (bits and self.direct and bmask >> 63 and N.probe_fold_needed(m, self.cap)):
+            return 0
+        if self._fold is None:
+            self._fold = torch.empty(N.kFoldWords, dtype=torch.int32, device=self.device)
+            N.probe_fold_build(bits, self.cap, ptr(self._fold), st)
+        return ptr(self._fold)
 
     # ------------------------------------------------------------ cpu helpers
     def _cpu_ranges(self, pkeys, pvalid):
