@@ -953,6 +953,22 @@ PYBIND11_MODULE(_native, m) {
                          uintptr_t s) {
     kern::str_fn_int(fn, P<uint8_t>(pat), plen, P<int64_t>(off), P<uint8_t>(chars), n, P<int32_t>(out), S(s));
   });
+  m.attr("LEV_FAST_MAX") = (int)kern::kLevFastMax;
+  m.def("str_pair_int", [](int fn, uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
+                           uintptr_t out, uintptr_t s) {
+    kern::str_pair_int(fn, P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob), P<const uint8_t>(cb),
+                       bb, n, P<int32_t>(out), S(s));
+  });
+  m.def("str_levenshtein", [](uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
+                              uintptr_t out, uintptr_t left, uintptr_t s) {
+    kern::str_levenshtein(P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob), P<const uint8_t>(cb),
+                          bb, n, P<int32_t>(out), P<int64_t>(left), S(s));
+  });
+  m.def("str_levenshtein_long", [](uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
+                                   uintptr_t out, uintptr_t scratch, int64_t lanes, int64_t cells, uintptr_t s) {
+    kern::str_levenshtein_long(P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob),
+                               P<const uint8_t>(cb), bb, n, P<int32_t>(out), P<int32_t>(scratch), lanes, cells, S(s));
+  });
   m.def("win_scan_tiles", &kern::win_scan_tiles);
   m.def("win_seg_scan", [](uintptr_t ids, bool ids64, uintptr_t ids2, bool ids2_64, uintptr_t vals, int vkind,
                            uintptr_t valid, int64_t n, int op, bool reverse, uintptr_t tflag, uintptr_t tval,

@@ -680,12 +680,12 @@ void win_index(int fn, int64_t arg, int64_t n, const int64_t* seg_start, const i
 // ---- strfunc.hip (scalar string functions over plain UTF-8 columns)
 enum StrFnCode {
   kSfTrim = 0, kSfReplace = 1, kSfLpad = 2, kSfRpad = 3, kSfReverse = 4, kSfRepeat = 5, kSfLeft = 6, kSfRight = 7,
-  kSfInitcap = 8, kSfTranslate = 9, kSfSplitPart = 10,
+  kSfInitcap = 8, kSfTranslate = 9, kSfSplitPart = 10, kSfSubstrIndex = 11,
   kSfStrpos = 20, kSfAscii = 21, kSfOctetLength = 22
 };
 struct StrFnArgs {
   int fn;
-  int64_t n1;              // trim mode bits (1 left, 2 right) / pad length / repeat count / left-right n / part
+  int64_t n1;              // trim mode bits (1 left, 2 right) / pad length / repeat count / left-right n / part / count
   const uint8_t* a;        // device bytes: trim set / search / fill / from-chars / delimiter
   int64_t alen;
   const uint8_t* b;        // device bytes: replacement / to-chars
@@ -699,6 +699,20 @@ void str_fn_copy(const StrFnArgs& a, const int64_t* off, const uint8_t* chars, i
                  uint8_t* out, int64_t out_cap, hipStream_t s);
 void str_fn_int(int fn, const uint8_t* pat, int64_t plen, const int64_t* off, const uint8_t* chars, int64_t n,
                 int32_t* out, hipStream_t s);
+
+// ---- strpair.hip (string functions of two string operands per row; either
+// side may be a one-row column broadcast to every row)
+enum StrPairCode { kSpStrpos = 0, kSpContains = 1, kSpStartsWith = 2, kSpEndsWith = 3, kSpFindInSet = 4 };
+// rows whose shorter side has at most this many characters keep their DP row in LDS
+constexpr int kLevFastMax = 127;
+void str_pair_int(int fn, const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb,
+                  int64_t n, int32_t* out, hipStream_t s);
+// left[2] (zeroed by the caller): rows written as -1, the largest shorter side (characters) among them
+void str_levenshtein(const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb,
+                     int64_t n, int32_t* out, int64_t* left, hipStream_t s);
+// fills the -1 rows; scratch: lanes * cells int32, a row needs (shorter side + 1) <= cells
+void str_levenshtein_long(const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb,
+                          int64_t n, int32_t* out, int32_t* scratch, int64_t lanes, int64_t cells, hipStream_t s);
 
 }  // namespace kern
 }  // namespace igloo

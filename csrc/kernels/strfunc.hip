@@ -1,7 +1,7 @@
 // Scalar string functions over plain (offsets + bytes) UTF-8 columns:
 // btrim / ltrim / rtrim, replace, lpad / rpad, reverse, repeat, left / right,
-// initcap, translate, split_part (string -> string) and strpos / ascii /
-// octet_length (string -> int32).
+// initcap, translate, split_part, substr_index (string -> string) and strpos /
+// ascii / octet_length (string -> int32).
 //
 // String -> string functions run in two passes over the rows, one lane per
 // row (grid-stride): pass 1 computes each output length with the SAME device
@@ -257,6 +257,45 @@ __device__ int64_t apply(const StrFnArgs& a, const uint8_t* s, int64_t n, uint8_
         } else {
           ++i;
         }
+      }
+      break;
+    }
+    case kSfSubstrIndex: {
+      // everything before the n1-th delimiter a.a counted from the left, or
+      // (n1 < 0) after the |n1|-th counted from the right; delimiters do not
+      // overlap, so the scan direction matters ('aaa' by 'aa')
+      if (n == 0 || a.alen == 0 || a.n1 == 0) break;
+      int64_t cnt = 0;
+      if (a.n1 > 0) {
+        int64_t end = n;
+        for (int64_t i = 0; i + a.alen <= n;) {
+          bool hit = true;
+          for (int64_t q = 0; hit && q < a.alen; ++q) hit = s[i + q] == a.a[q];
+          if (!hit) {
+            ++i;
+          } else if (++cnt == a.n1) {
+            end = i;
+            break;
+          } else {
+            i += a.alen;
+          }
+        }
+        e.bytes(s, end);
+      } else {
+        int64_t start = 0;
+        for (int64_t i = n - a.alen; i >= 0;) {
+          bool hit = true;
+          for (int64_t q = 0; hit && q < a.alen; ++q) hit = s[i + q] == a.a[q];
+          if (!hit) {
+            --i;
+          } else if (--cnt == a.n1) {
+            start = i + a.alen;
+            break;
+          } else {
+            i -= a.alen;
+          }
+        }
+        e.bytes(s + start, n - start);
       }
       break;
     }

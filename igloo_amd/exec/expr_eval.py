@@ -514,6 +514,15 @@ class Evaluator:
             from ..ops import strfuncs as SF
             c = args[0]
             return SF.apply(c, name, e.options)
+        if name in _STRPAIR and len(args) == 2:
+            # two string operands per row (ops/strfuncs.py apply_pair): a
+            # constant operand stays a constant, NULL makes every row NULL
+            from ..ops import strfuncs as SF
+            if any(isinstance(a, Scalar) and a.value is None for a in args):
+                return Column.full(None, e.dtype, b.num_rows, self.device(b))
+            x, y = [str(a.value) if isinstance(a, Scalar) else a for a in args]
+            out, valid = SF.apply_pair(x, y, name, b.num_rows)
+            return Column(e.dtype, out, valid)
         if name in ("strpos", "ascii", "octet_length"):
             from ..ops import strfuncs as SF
             c = args[0]
@@ -749,6 +758,9 @@ class Evaluator:
             return Scalar(abs(vals[0]), e.dtype)
         if name == "concat":
             return Scalar(str(vals[0]) + str(vals[1]), T.UTF8)
+        if name in _STRPAIR and len(vals) == 2:
+            from ..ops import strfuncs as SF
+            return Scalar(SF.py_fn2(name)(str(vals[0]), str(vals[1])), e.dtype)
         if name == "round":
             if e.dtype.is_decimal:
                 s = args[0].dtype.scale
@@ -817,7 +829,9 @@ class Evaluator:
 
 
 _STRFN = ("trim", "replace", "lpad", "rpad", "reverse", "repeat", "left", "right", "initcap", "translate",
-          "split_part")
+          "split_part", "substr_index")
+# with two arguments: the per-row forms (one-argument strpos keeps its literal in the options)
+_STRPAIR = ("levenshtein", "strpos", "contains", "starts_with", "ends_with", "find_in_set")
 _MATH1 = ("sign", "trunc", "log2", "cbrt", "degrees", "radians", "sin", "cos", "tan", "asin", "acos", "atan", "sinh",
           "cosh", "tanh", "isnan", "iszero", "factorial")
 _US_DAY = 86_400_000_000

@@ -1,6 +1,9 @@
 """Scalar string functions (csrc/kernels/strfunc.hip): btrim / ltrim / rtrim,
 replace, lpad / rpad, reverse, repeat, left / right, initcap, translate,
-split_part, strpos, ascii, octet_length; regexp_like / regexp_count /
+split_part, substr_index, strpos, ascii, octet_length; the functions of two
+string operands per row (csrc/kernels/strpair.hip, ``apply_pair``):
+levenshtein, contains, find_in_set and strpos / starts_with / ends_with with a
+per-row second operand, either operand a column or a constant; regexp_like / regexp_count /
 regexp_replace / regexp_match (csrc/kernels/regex.hip: a DFA of the pattern
 walked per row; regexp_count, regexp_replace with a literal replacement and
 regexp_match without capture groups find leftmost-first match spans there.
@@ -30,8 +33,17 @@ from ._lib import is_gpu, launch, native, ptr, stream
 from .select import offsets_from_lengths
 
 CODES = {"trim": 0, "replace": 1, "lpad": 2, "rpad": 3, "reverse": 4, "repeat": 5, "left": 6, "right": 7,
-         "initcap": 8, "translate": 9, "split_part": 10}
+         "initcap": 8, "translate": 9, "split_part": 10, "substr_index": 11}
 INT_CODES = {"strpos": 20, "ascii": 21, "octet_length": 22}
+#: two-operand functions of strpair.hip str_pair_int (levenshtein has kernels of its own)
+PAIR_CODES = {"strpos": 0, "contains": 1, "starts_with": 2, "ends_with": 3, "find_in_set": 4}
+PAIR_FUNCS = ("levenshtein",) + tuple(PAIR_CODES)
+PAIR_BOOL = ("contains", "starts_with", "ends_with")
+#: worker lanes of the long-row edit-distance kernel (each owns a slab of the scratch)
+LEV_LONG_LANES = 1024
+#: bound of that scratch in bytes: fewer lanes work when the rows are long, so
+#: it holds max(this, 4 * (longest shorter side + 1)) bytes whatever the data
+LEV_LONG_SCRATCH = 256 << 20
 
 
 # ------------------------------------------------------------ Python semantics
@@ -101,6 +113,15 @@ def py_fn(name: str, opts: tuple) -> Callable[[str], object]:
             idx = n - 1 if n > 0 else len(parts) + n
             return parts[idx] if 0 <= idx < len(parts) and n != 0 else ""
         return sp
+    if name == "substr_index":
+        d, n = opts
+        n = int(n)
+
+        def si(s):
+            if not s or not d or n == 0:
+                return ""
+            return d.join(s.split(d)[:n]) if n > 0 else d.join(s.rsplit(d)[n:])
+        return si
     if name == "strpos":
         sub = opts[0]
         return lambda s: s.find(sub) + 1
@@ -142,7 +163,7 @@ def apply(col: Column, name: str, opts: tuple) -> Column:
         n1 = int(opts[0])
     elif name == "translate":
         a, b = opts
-    elif name == "split_part":
+    elif name in ("split_part", "substr_index"):
         a, n1 = opts[0], int(opts[1])
     ta, tb = _dev_bytes(a, col.device), _dev_bytes(b, col.device)
     la, lb = len(a.encode("utf-8")), len(b.encode("utf-8"))
@@ -176,6 +197,117 @@ def apply_int(col: Column, name: str, opts: tuple) -> torch.Tensor:
     out = torch.empty(n, dtype=torch.int32, device=col.device)
     launch("str_fn_int").str_fn_int(INT_CODES[name], ptr(tp), len(pat.encode("utf-8")), ptr(col.offsets),
                                     ptr(col.data), n, ptr(out), stream(out))
+    return out
+
+
+# ------------------------------------------------- two string operands per row
+def _py_levenshtein(a: str, b: str) -> int:
+    if len(a) > len(b):
+        a, b = b, a
+    row = list(range(len(a) + 1))
+    for i, cb in enumerate(b, 1):
+        diag, row[0] = row[0], i
+        for j, ca in enumerate(a, 1):
+            diag, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, diag + (ca != cb))
+    return row[len(a)]
+
+
+def py_fn2(name: str) -> Callable[[str, str], object]:
+    """Python definition of a two-operand function (the CPU engine and the
+    binder's constant folding)."""
+    if name == "levenshtein":
+        return _py_levenshtein
+    if name == "strpos":
+        return lambda a, b: a.find(b) + 1
+    if name == "contains":
+        return lambda a, b: b in a
+    if name == "starts_with":
+        return lambda a, b: a.startswith(b)
+    if name == "ends_with":
+        return lambda a, b: a.endswith(b)
+    if name == "find_in_set":
+        def fis(a, lst):
+            parts = lst.split(",")
+            return parts.index(a) + 1 if a in parts else 0
+        return fis
+    raise KeyError(name)
+
+
+def apply_pair(a, b, name: str, n: Optional[int] = None):
+    """Two-operand function ``name`` over ``n`` rows: (result tensor, combined
+    validity or None). int32 for levenshtein / strpos / find_in_set, bool for
+    contains / starts_with / ends_with; NULL rows hold an unspecified value.
+    An operand is a string column or a Python ``str`` (a constant); a one-row
+    column is broadcast when ``n`` says so. A dictionary column against a
+    constant runs over its dictionary and maps the result through the codes;
+    two columns are decoded and walked row by row (strpair.hip)."""
+    from .strings import _dict_lut_dev, const_column, decode
+    dev = (a if isinstance(a, Column) else b).device
+    const_a, const_b = isinstance(a, str), isinstance(b, str)
+    ca = const_column(a, dev) if const_a else a
+    cb = const_column(b, dev) if const_b else b
+    if n is None:
+        n = len(cb) if const_a else len(ca) if const_b else max(len(ca), len(cb))
+    ba, bb = len(ca) == 1 and n != 1, len(cb) == 1 and n != 1
+    va = None if ca.valid is None else (ca.valid.expand(n) if ba else ca.valid)
+    vb = None if cb.valid is None else (cb.valid.expand(n) if bb else cb.valid)
+    valid = va if vb is None else (vb if va is None else va & vb)
+    valid = valid.contiguous() if valid is not None else None
+    as_bool = name in PAIR_BOOL
+    if not is_gpu(ca.data) or not is_gpu(cb.data):
+        fn = py_fn2(name)
+        xs, ys = ca.to_arrow().to_pylist(), cb.to_arrow().to_pylist()
+        xs, ys = (xs * n if ba else xs), (ys * n if bb else ys)
+        vals = [0 if x is None or y is None else fn(x, y) for x, y in zip(xs, ys)]
+        return torch.tensor(vals, dtype=torch.bool if as_bool else torch.int32, device=dev), valid
+    if const_b and ca.is_dict and not const_a:
+        out = _dict_lut_dev(ca, ("strpair", name, 0, b), lambda d: _lut_build(d, cb, False, name))
+    elif const_a and cb.is_dict and not const_b:
+        out = _dict_lut_dev(cb, ("strpair", name, 1, a), lambda d: _lut_build(ca, d, True, name))
+    else:
+        out = _pair_dev(decode(ca), decode(cb), ba, bb, n, name)
+    return (out != 0 if as_bool else out), valid
+
+
+def _lut_build(a: Column, b: Column, const_first: bool, name: str) -> torch.Tensor:
+    """Per-entry result over a dictionary (the other side a one-row
+    constant). Outside a graph capture the table is kept on the dictionary
+    (strings.py _dict_lut_dev), so its readback (levenshtein's long-row
+    counter) is a one-time build and stays out of the speculation log."""
+    from ._lib import capturing, unlogged
+    n = len(a) if not const_first else len(b)
+    ba, bb = const_first and n != 1, (not const_first) and n != 1
+    if capturing() or name != "levenshtein":
+        return _pair_dev(a, b, ba, bb, n, name)
+    with unlogged():
+        return _pair_dev(a, b, ba, bb, n, name)
+
+
+def _pair_dev(a: Column, b: Column, ba: bool, bb: bool, n: int, name: str) -> torch.Tensor:
+    """int32 result of ``name`` over plain device string columns (0 / 1 for
+    the boolean functions); ``ba`` / ``bb``: that side is one row for all."""
+    from ._lib import to_host_ints
+    dev = a.device
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out
+    s = stream(out)
+    sides = (ptr(a.offsets), ptr(a.data), ba, ptr(b.offsets), ptr(b.data), bb, n)
+    if name != "levenshtein":
+        launch("str_pair").str_pair_int(PAIR_CODES[name], *sides, ptr(out), s)
+        return out
+    # rows whose DP row fits LDS are answered at once; the kernel counts the
+    # others (written as -1) and the longest shorter side among them
+    left = torch.zeros(2, dtype=torch.int64, device=dev)
+    launch("str_lev").str_levenshtein(*sides, ptr(out), ptr(left), s)
+    rows, longest = to_host_ints(left)
+    if rows:
+        # one slab of (longest + 1) int32 cells per worker lane, LEV_LONG_SCRATCH
+        # bytes at the most in all (a single slab longer than that: one lane)
+        cells = longest + 1
+        lanes = max(1, min(LEV_LONG_LANES, -(-rows // 64) * 64, LEV_LONG_SCRATCH // (4 * cells)))
+        scratch = torch.empty(lanes * cells, dtype=torch.int32, device=dev)
+        launch("str_lev").str_levenshtein_long(*sides, ptr(out), ptr(scratch), lanes, cells, s)
     return out
 
 

@@ -1557,6 +1557,21 @@ class Binder:
             if isinstance(a, Lit):
                 return Lit(None if a.value is None else SF.py_fn(fname, opts)(a.value), rt)
             return Func(fname, [a], rt, opts)
+
+        def pairfn(fname, rt):
+            # two string operands per row (ops/strfuncs.py apply_pair): each a
+            # column, an expression or a constant; all-constant calls fold here
+            _nargs(name, args, 2)
+            a, b = self._coerce(args[0], UTF8), self._coerce(args[1], UTF8)
+            if isinstance(a, Lit) and isinstance(b, Lit):
+                if a.value is None or b.value is None:
+                    return Lit(None, rt)
+                return Lit(SF.py_fn2(fname)(a.value, b.value), rt)
+            return Func(fname, [a, b], rt)
+
+        def per_row(i):
+            # the call has exactly two arguments and the i-th is no string literal
+            return len(args) == 2 and not (isinstance(args[i], Lit) and isinstance(args[i].value, str))
         if not args and name not in ("pi", "random", "now", "current_timestamp", "current_date", "today",
                                      "uuid", "current_time"):
             raise PlanError(f"{name}() needs arguments")
@@ -1578,7 +1593,18 @@ class Binder:
             return strfn("translate", (lit_str(1, "from"), lit_str(2, "to")))
         if name == "split_part":
             return strfn("split_part", (lit_str(1, "delimiter"), lit_int(2, "part")))
+        if name in ("substr_index", "substring_index"):
+            _nargs(name, args, 3)
+            return strfn("substr_index", (lit_str(1, "delimiter"), lit_int(2, "count")))
+        if name == "levenshtein":
+            return pairfn("levenshtein", INT32)
+        if name == "find_in_set":
+            return pairfn("find_in_set", INT32)
+        if name == "contains":
+            return pairfn("contains", BOOL)
         if name in ("strpos", "instr"):
+            if per_row(1):
+                return pairfn("strpos", INT32)
             return strfn("strpos", (lit_str(1, "substring"),), INT32)
         if name == "ascii":
             return strfn("ascii", (), INT32)
@@ -1587,6 +1613,8 @@ class Binder:
         if name == "bit_length":
             return BinOp("*", Cast(strfn("octet_length", (), INT32), INT64), Lit(8, INT64), INT64)
         if name in ("starts_with", "ends_with"):
+            if per_row(1):
+                return pairfn(name, BOOL)
             p = _like_escape(lit_str(1, "prefix"))
             return Like(self._coerce(args[0], UTF8), p + "%" if name == "starts_with" else "%" + p)
         if name == "concat_ws":

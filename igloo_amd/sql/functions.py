@@ -26,6 +26,9 @@ STRING: Dict[str, str] = {
     "ends_with": "ends_with(s, 'c')", "regexp_like": "regexp_like(s, '^a.*c$')",
     "regexp_replace": "regexp_replace(s, '[aeiou]', '_', 'g')", "regexp_count": "regexp_count(s, '[a-c]', 2, 'i')",      # (str, pattern[, start][, flags])
     "chr": "chr(65)", "to_hex": "to_hex(255)",
+    "levenshtein": "levenshtein(s, reverse(s))", "contains": "contains(s, 'ab')",
+    "find_in_set": "find_in_set(s, 'abc,caba')", "substr_index": "substr_index(s, ' ', 2)",
+    "substring_index": "substring_index(s, 'b', -1)",
 }
 NUMERIC: Dict[str, str] = {
     "abs": "abs(n - 3)", "round": "round(f, 1)", "ceil": "ceil(f)", "ceiling": "ceiling(f)", "floor": "floor(f)",
