@@ -20,6 +20,13 @@
 //                 parallel, strings with escapes decoded by lane 0
 //                 (\" \\ \/ \b \f \n \r \t and \uXXXX with surrogate pairs,
 //                 written as UTF-8).
+//
+// Strictness: any other escape, and a \uD800-\uDFFF escape that is not a high
+// surrogate followed at once by a low one, is a syntax error of the record
+// (scan_string fails, in skipped values too), so no invalid UTF-8 is ever
+// written; arrow-json rejects such records as well. A key that contains an
+// escape is not decoded: the record raises (JSON_ERR_KEY) instead of its
+// column silently turning NULL.
 #include "common.h"
 #include "kernels.h"
 #include "textparse.h"
@@ -29,7 +36,7 @@ namespace kern {
 
 namespace {
 
-enum : int { JSON_ERR_SYNTAX = 1, JSON_ERR_VALUE = 2, JSON_ERR_FIELDS = 3 };
+enum : int { JSON_ERR_SYNTAX = 1, JSON_ERR_VALUE = 2, JSON_ERR_FIELDS = 3, JSON_ERR_KEY = 4 };
 
 __device__ inline void jset_err(int* err, int code) { atomicCAS(err, 0, code); }
 
@@ -57,7 +64,8 @@ __device__ inline int64_t u4(const uint8_t* p, const uint8_t* e) {
 }
 
 // Scans a JSON string whose opening quote is at p. Returns the position of the
-// closing quote (or -1), the decoded UTF-8 length and whether escapes occur.
+// closing quote (or null: unterminated, a bad escape or an unpaired surrogate),
+// the decoded UTF-8 length and whether escapes occur.
 __device__ inline const uint8_t* scan_string(const uint8_t* p, const uint8_t* e, int64_t* out_len, bool* esc) {
   int64_t len = 0;
   bool any = false;
@@ -79,15 +87,17 @@ __device__ inline const uint8_t* scan_string(const uint8_t* p, const uint8_t* e,
       int64_t cp = u4(q + 1, e);
       if (cp < 0) return nullptr;
       q += 5;
-      if (cp >= 0xD800 && cp < 0xDC00 && q + 2 < e && q[1] == '\\' && q[2] == 'u') {
+      if (cp >= 0xD800 && cp < 0xE000) {
+        // a high surrogate and its low half, or nothing
+        if (cp >= 0xDC00 || !(q + 2 < e && q[1] == '\\' && q[2] == 'u')) return nullptr;
         const int64_t lo = u4(q + 2, e);
-        if (lo >= 0xDC00 && lo < 0xE000) {
-          cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
-          q += 6;
-        }
+        if (lo < 0xDC00 || lo >= 0xE000) return nullptr;
+        cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
+        q += 6;
       }
       len += utf8_bytes((uint32_t)cp);
     } else {
+      if (x != '"' && x != '\\' && x != '/' && x != 'b' && x != 'f' && x != 'n' && x != 'r' && x != 't') return nullptr;
       ++q;
       ++len;
     }
@@ -152,6 +162,7 @@ __global__ __launch_bounds__(kBlock) void json_parse_kernel(const uint8_t* __res
       const uint8_t* kq = scan_string(p, e, &kl, &kesc);
       if (!kq) { bad = true; break; }
       const uint8_t* ks = p + 1;
+      if (kesc) jset_err(err, JSON_ERR_KEY);
       const int f = kesc ? -1 : find_field(ks, kq - ks, names, name_off, ncols);
       p = kq + 1;
       while (p < e && is_ws(*p)) ++p;

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "pow5_table.h"
 
 namespace igloo {
 namespace kern {
@@ -33,13 +34,15 @@ __device__ inline bool parse_int(const uint8_t* p, const uint8_t* e, int64_t* ou
   return true;
 }
 
-// exact fixed point: digits[.digits] scaled to `scale` fractional digits
+// exact fixed point: digits[.digits] scaled to `scale` fractional digits; at
+// least one digit, leading zeros free, at most 36 significant digits
 __device__ inline bool parse_decimal(const uint8_t* p, const uint8_t* e, int scale, int64_t* out) {
   bool neg = false;
   if (p < e && (*p == '-' || *p == '+')) neg = *p++ == '-';
   if (p >= e) return false;
   __int128 v = 0;
   int frac = -1, digits = 0;
+  bool any = false;
   for (; p < e; ++p) {
     if (*p == '.') {
       if (frac >= 0) return false;
@@ -48,6 +51,7 @@ __device__ inline bool parse_decimal(const uint8_t* p, const uint8_t* e, int sca
     }
     const unsigned d = (unsigned)*p - '0';
     if (d > 9) return false;
+    any = true;
     if (frac >= 0) {
       if (frac == scale) {
         if (d != 0) return false;  // more fractional digits than the scale: not exact
@@ -56,66 +60,305 @@ __device__ inline bool parse_decimal(const uint8_t* p, const uint8_t* e, int sca
       ++frac;
     }
     v = v * 10 + d;
-    if (++digits > 36) return false;
+    if (v != 0 && ++digits > 36) return false;
   }
-  for (int f = frac < 0 ? 0 : frac; f < scale; ++f) v *= 10;
+  if (!any) return false;
+  for (int f = frac < 0 ? 0 : frac; f < scale; ++f) {
+    if (v > (__int128)INT64_MAX) return false;   // out of range already: never wraps
+    v *= 10;
+  }
   if (neg) v = -v;
   if (v > (__int128)INT64_MAX || v < (__int128)INT64_MIN) return false;
   *out = (int64_t)v;
   return true;
 }
 
-__device__ inline bool parse_f64(const uint8_t* p, const uint8_t* e, double* out) {
-  bool neg = false;
-  if (p < e && (*p == '-' || *p == '+')) neg = *p++ == '-';
-  if (p >= e) return false;
-  uint64_t m = 0;
-  int sig = 0, e10 = 0;
-  bool any = false, dot = false;
-  for (; p < e; ++p) {
+__device__ inline bool ieq(const uint8_t* p, const uint8_t* e, const char* lit) {
+  int k = 0;
+  for (; p + k < e; ++k) {
+    if (!lit[k]) return false;
+    uint8_t c = p[k];
+    if (c >= 'A' && c <= 'Z') c += 32;
+    if (c != (uint8_t)lit[k]) return false;
+  }
+  return lit[k] == 0;
+}
+
+// ---- float64 parsing, correctly rounded (round half to even) for every input.
+//
+//   fast path   at most 19 digits, all of them kept, w < 2^53 and |e10| <= 22:
+//               w and 10^|e10| are exact doubles, so one multiply or divide
+//               rounds once (Clinger).
+//   slow path   integer only, so host and device agree bit for bit. The value
+//               is w * 10^q (w: the first 19 significant digits). With the
+//               truncated 128-bit power T of kPow5, 5^q = (T + d) * 2^k with
+//               0 <= d < 1, so the exact 192-bit product P = w' * T (w' = w
+//               normalised to 64 bits) brackets the value: P <= V < P + 2^64
+//               in units of the product's low end (V == P where T is exact).
+//               When digits were dropped, the upper bound is taken from w + 1.
+//               Both ends are rounded to a double; rounding is monotonic, so
+//               when they agree that double is the answer.
+//   exact path  when the ends round differently (the value is within about
+//               2^-127 of a rounding boundary, or 2^-59 with dropped digits:
+//               ties, and every 60th or so long input), the digits themselves
+//               (up to kBigDigits of them plus a sticky flag; no boundary
+//               between doubles has more than 768 significant digits) are
+//               compared as a big integer with the midpoint above each
+//               candidate. Never taken on shortest round-trip or %.17e text.
+constexpr uint64_t kF64Inf = 0x7FF0000000000000ULL;
+constexpr uint64_t kF64NaN = 0x7FF8000000000000ULL;
+
+// (a2:a1:a0) * 2^(e - 191) with bit 63 of a2 set, i.e. a value in [2^e, 2^(e+1)),
+// to the bits of the nearest double (ties to even); a1 and a0 are sticky only
+__device__ inline uint64_t f64_round_bits(uint64_t a2, uint64_t a1, uint64_t a0, int e) {
+  if (e > 1023) return kF64Inf;
+  int shift = 11;                       // 64 - 53 kept bits
+  if (e < -1022) {                      // subnormal: fewer kept bits
+    shift += -1022 - e;
+    if (shift > 64) return 0;           // below half the smallest subnormal
+  }
+  uint64_t m, rb, st;
+  if (shift == 64) {
+    m = 0;
+    rb = a2 >> 63;
+    st = a2 << 1;
+  } else {
+    m = a2 >> shift;
+    rb = (a2 >> (shift - 1)) & 1;
+    st = a2 << (65 - shift);
+  }
+  st |= a1 | a0;
+  m += rb & (uint64_t)((st != 0) | (m & 1));
+  if (e < -1022) return m;              // m == 2^52 is the smallest normal: the same bits
+  uint64_t be = (uint64_t)(e + 1023);
+  if (m >> 53) {
+    m >>= 1;
+    ++be;
+  }
+  if (be >= 2047) return kF64Inf;
+  return (be << 52) | (m & 0xFFFFFFFFFFFFFULL);
+}
+
+// the double nearest the lower (upper == false) or upper end of the bracket of
+// w * 10^q; w != 0, kPow5MinQ <= q <= kPow5MaxQ
+__device__ inline uint64_t f64_scale_bits(uint64_t w, int q, bool upper) {
+  const int lz = __builtin_clzll(w);
+  w <<= lz;
+  const uint64_t th = kPow5[q - kPow5MinQ][0], tl = kPow5[q - kPow5MinQ][1];
+  const unsigned __int128 ph = (unsigned __int128)w * th, pl = (unsigned __int128)w * tl;
+  uint64_t a0 = (uint64_t)pl;
+  uint64_t a1 = (uint64_t)ph + (uint64_t)(pl >> 64);
+  uint64_t a2 = (uint64_t)(ph >> 64) + (a1 < (uint64_t)ph);
+  // 5^q = (T + d) * 2^(b - 127), b = floor(log2 5^q) (scripts/gen_pow5_table.py checks the formula)
+  int e = 64 + ((152170 * q) >> 16) + q - lz;
+  if (upper && !(q >= 0 && q <= kPow5ExactMaxQ)) {
+    if (++a1 == 0 && ++a2 == 0) {       // the bound reached 2^192
+      a2 = 1ULL << 63;
+      ++e;
+    }
+  }
+  if (!(a2 >> 63)) {
+    a2 = (a2 << 1) | (a1 >> 63);
+    a1 = (a1 << 1) | (a0 >> 63);
+    a0 <<= 1;
+    --e;
+  }
+  return f64_round_bits(a2, a1, a0, e);
+}
+
+// little-endian big integer of fixed capacity; every operation is bounded by it
+constexpr int kBigWords = 90;           // 2880 bits; the comparison needs < 2^2640
+constexpr int kBigDigits = 774;         // > 768 + 1, a multiple of 9
+struct BigU {
+  uint32_t w[kBigWords];
+  int n;
+};
+
+__device__ inline void big_muladd(BigU& b, uint32_t m, uint32_t a) {
+  uint64_t c = a;
+  for (int i = 0; i < b.n; ++i) {
+    c += (uint64_t)b.w[i] * m;
+    b.w[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  if (c && b.n < kBigWords) b.w[b.n++] = (uint32_t)c;
+}
+
+__device__ inline void big_mul_pow5(BigU& b, int64_t k) {
+  for (; k >= 13; k -= 13) big_muladd(b, 1220703125u, 0);   // 5^13
+  uint32_t m = 1;
+  for (; k > 0; --k) m *= 5;
+  if (m > 1) big_muladd(b, m, 0);
+}
+
+__device__ inline void big_shl(BigU& b, int64_t s) {
+  const int ws = (int)(s >> 5), bs = (int)(s & 31);
+  if (b.n == 0 || b.n + ws + 1 > kBigWords) return;
+  b.w[b.n] = 0;
+  for (int i = b.n; i >= 0; --i) {
+    const uint64_t v = ((uint64_t)b.w[i] << bs) | (bs && i ? b.w[i - 1] >> (32 - bs) : 0);
+    b.w[i + ws] = (uint32_t)v;
+  }
+  for (int i = 0; i < ws; ++i) b.w[i] = 0;
+  b.n += ws + 1;
+  while (b.n && !b.w[b.n - 1]) --b.n;
+}
+
+__device__ inline int big_cmp(const BigU& a, const BigU& b) {
+  if (a.n != b.n) return a.n < b.n ? -1 : 1;
+  for (int i = a.n - 1; i >= 0; --i)
+    if (a.w[i] != b.w[i]) return a.w[i] < b.w[i] ? -1 : 1;
+  return 0;
+}
+
+// Sign of (digits [p, pe) * 10^x) - (midpoint between the doubles of bits `lo` and lo + 1)
+__device__ inline int f64_cmp_midpoint(uint64_t lo, const uint8_t* p, const uint8_t* pe, int64_t x) {
+  BigU D, R;
+  D.n = 0;
+  int nd = 0;
+  bool dot = false, sticky = false;
+  uint32_t chunk = 0, cm = 1;
+  for (; p < pe; ++p) {
     const uint8_t c = *p;
     if (c == '.') {
-      if (dot) return false;
       dot = true;
       continue;
     }
     const unsigned d = (unsigned)c - '0';
-    if (d > 9) break;
-    any = true;
-    if (sig < 19) {
-      if (m || d) ++sig;
-      m = m * 10 + d;
-      if (dot) --e10;
-    } else if (!dot) {
-      ++e10;
+    if (nd == 0 && d == 0) {
+      if (dot) --x;
+      continue;
+    }
+    if (nd < kBigDigits) {
+      chunk = chunk * 10 + d;
+      cm *= 10;
+      ++nd;
+      if (dot) --x;
+      if (cm == 1000000000u) {
+        big_muladd(D, cm, chunk);
+        chunk = 0;
+        cm = 1;
+      }
+    } else {
+      sticky |= d != 0;
+      if (!dot) ++x;
     }
   }
-  if (!any) return false;
-  if (p < e) {
-    if (*p != 'e' && *p != 'E') return false;
-    ++p;
-    int64_t x;
-    if (!parse_int(p, e, &x) || x > 400 || x < -400) return false;
-    e10 += (int)x;
+  if (cm > 1) big_muladd(D, cm, chunk);
+  // the caller's bracket puts the value next to this midpoint, so -1110 < x < 310
+  if (x > 400) return 1;
+  if (x < -1200) return -1;
+  const uint64_t be = lo >> 52, frac = lo & 0xFFFFFFFFFFFFFULL;
+  const uint64_t m2 = 2 * (be ? frac | (1ULL << 52) : frac) + 1;   // midpoint = m2 * 2^k
+  const int64_t k = (be ? (int64_t)be - 1075 : -1074) - 1;
+  R.w[0] = (uint32_t)m2;
+  R.w[1] = (uint32_t)(m2 >> 32);
+  R.n = R.w[1] ? 2 : 1;
+  // D * 5^x * 2^x  <>  R * 2^k
+  if (x >= 0) big_mul_pow5(D, x);
+  else big_mul_pow5(R, -x);
+  if (x - k > 0) big_shl(D, x - k);
+  else if (k - x > 0) big_shl(R, k - x);
+  const int c = big_cmp(D, R);
+  return c == 0 && sticky ? 1 : c;
+}
+
+__device__ __noinline__ static uint64_t f64_exact_bits(uint64_t lo, uint64_t hi, const uint8_t* p, const uint8_t* pe,
+                                                int64_t x) {
+  // lo <= answer <= hi; hi == lo + 1 (the bracket is far narrower than one ulp)
+  for (; lo < hi; ++lo) {
+    const int c = f64_cmp_midpoint(lo, p, pe, x);
+    if (c < 0) return lo;
+    if (c == 0) return lo + (lo & 1);
   }
-  double v = (double)m;
-  // exact when m < 2^53 and |e10| <= 22 (both factors exactly representable)
-  const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                          1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-  if (e10 > 0) {
-    while (e10 > 22) {
-      v *= 1e22;
-      e10 -= 22;
+  return hi;
+}
+
+__device__ inline bool parse_f64(const uint8_t* p, const uint8_t* e, double* out) {
+  bool neg = false;
+  if (p < e && (*p == '-' || *p == '+')) neg = *p++ == '-';
+  if (p >= e) return false;
+  uint64_t bits;
+  const uint8_t c0 = *p | 0x20;
+  if (c0 == 'i' || c0 == 'n') {
+    // the spellings Arrow and DataFusion read, any case
+    if (ieq(p, e, "inf") || ieq(p, e, "infinity")) bits = kF64Inf;
+    else if (ieq(p, e, "nan")) bits = kF64NaN;
+    else return false;
+  } else {
+    const uint8_t* dstart = p;
+    // integers, not flags, in the loop: lanes diverge here, and a flag carried
+    // through divergent code costs a mask merge per iteration
+    uint64_t w = 0;
+    int sig = 0;            // significant digits in w
+    int64_t nd = 0;         // digits seen
+    int64_t nkept = 0;      // digits folded into w, leading zeros included
+    int64_t nint = -1;      // digits before the point, -1: no point yet
+    unsigned dropped = 0;   // OR of the digits that did not fit
+    for (; p < e; ++p) {
+      const uint8_t c = *p;
+      const unsigned d = (unsigned)c - '0';
+      if (d <= 9) {
+        if (sig < 19) {
+          w = w * 10 + d;
+          sig += w != 0;
+          ++nkept;
+        } else {
+          dropped |= d;
+        }
+        ++nd;
+      } else if (c == '.' && nint < 0) {
+        nint = nd;
+      } else {
+        break;              // a second point ends the digits and is no exponent mark: rejected below
+      }
     }
-    v *= p10[e10];
-  } else if (e10 < 0) {
-    while (e10 < -22) {
-      v /= 1e22;
-      e10 += 22;
+    if (nd == 0) return false;
+    const bool trunc = dropped != 0;
+    if (nint < 0) nint = nd;
+    // kept digits after the point scale down, dropped digits before it scale up
+    int64_t e10 = nint - nkept;
+    const uint8_t* dend = p;
+    int64_t x = 0;
+    if (p < e) {
+      if ((*p | 0x20) != 'e') return false;
+      ++p;
+      bool xneg = false;
+      if (p < e && (*p == '-' || *p == '+')) xneg = *p++ == '-';
+      if (p >= e) return false;
+      for (; p < e; ++p) {
+        const unsigned d = (unsigned)*p - '0';
+        if (d > 9) return false;
+        if (x < ((int64_t)1 << 40)) x = x * 10 + d;   // clamped, never rejected
+      }
+      if (xneg) x = -x;
+      e10 += x;
     }
-    v /= p10[-e10];
+    if (w == 0) {
+      bits = 0;
+    } else if (!trunc && w < (1ULL << 53) && e10 >= -22 && e10 <= 22) {
+      // exact: both factors are representable, one rounding
+      const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                              1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+      double v = (double)w;
+      if (e10 > 0) v *= p10[e10];
+      else if (e10 < 0) v /= p10[-e10];
+      *out = neg ? -v : v;
+      return true;
+    } else if (e10 > kPow5MaxQ) {
+      bits = kF64Inf;                   // w >= 1
+    } else if (e10 < kPow5MinQ) {
+      bits = 0;                         // (w + 1) * 10^e10 <= 10^-325, below half the smallest subnormal
+    } else {
+      const uint64_t lo = f64_scale_bits(w, (int)e10, false);
+      const uint64_t hi = f64_scale_bits(w + trunc, (int)e10, true);
+      bits = lo == hi ? lo : f64_exact_bits(lo, hi, dstart, dend, x);
+    }
   }
-  *out = neg ? -v : v;
+  if (neg) bits |= 1ULL << 63;
+  double v;
+  __builtin_memcpy(&v, &bits, sizeof v);
+  *out = v;
   return true;
 }
 
@@ -137,20 +380,12 @@ __device__ inline bool parse_date(const uint8_t* p, const uint8_t* e, int32_t* o
     if (c > 9) return false;
     d = d * 10 + c;
   }
-  if (m < 1 || m > 12 || d < 1 || d > 31) return false;
+  if (m < 1 || m > 12 || d < 1) return false;
+  const bool leap = y % 4 == 0 && (y % 100 != 0 || y % 400 == 0);
+  const int64_t dim = m == 2 ? (leap ? 29 : 28) : (m == 4 || m == 6 || m == 9 || m == 11) ? 30 : 31;
+  if (d > dim) return false;
   *out = (int32_t)days_from_civil(y, m, d);
   return true;
-}
-
-__device__ inline bool ieq(const uint8_t* p, const uint8_t* e, const char* lit) {
-  int k = 0;
-  for (; p + k < e; ++k) {
-    if (!lit[k]) return false;
-    uint8_t c = p[k];
-    if (c >= 'A' && c <= 'Z') c += 32;
-    if (c != (uint8_t)lit[k]) return false;
-  }
-  return lit[k] == 0;
 }
 
 // days since 1970-01-01 -> civil date (H. Hinnant's algorithm)

@@ -1,6 +1,7 @@
 // Host stand-in for common.h: lets csrc/tools/strpair_host.cpp compile the device routines of
 // strpair.hip / strfunc.hip as plain C++ (one "thread" after another) under ASan / UBSan.
-// tests/test_strpair_host.py copies it next to copies of the two kernel files as common.h.
+// tests/test_strpair_host.py copies it next to copies of the two kernel files as common.h;
+// csrc/tools/textparse_host.cpp (tests/test_textparse_host.py) uses it the same way for textparse.h.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -12,6 +13,8 @@
 #define __host__
 #define __forceinline__ inline
 #define __launch_bounds__(x)
+#define __constant__
+#define __noinline__ __attribute__((noinline))
 #define __shared__ static
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1) : x(a), y(1), z(1) {} };
 static dim3 blockIdx, threadIdx, blockDim, gridDim;

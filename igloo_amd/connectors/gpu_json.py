@@ -18,7 +18,8 @@ from ..utils.errors import IoError
 from .gpu_csv import KIND
 
 ERRORS = {1: "malformed JSON record", 2: "value does not parse as the column type",
-          3: "a record lacks a non-nullable field"}
+          3: "a record lacks a non-nullable field",
+          4: "a key contains an escape sequence (the GPU parser matches keys byte for byte)"}
 MAX_FIELDS = 64
 
 

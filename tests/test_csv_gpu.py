@@ -4,6 +4,7 @@ lines, NULLs, every type the engine parses (int32/int64/decimal/float64/
 date/bool/utf8), and a value that does not parse (host fallback)."""
 import decimal
 import os
+import struct
 
 import numpy as np
 import pyarrow as pa
@@ -35,7 +36,9 @@ def _compare(got, ref, fields):
         want = Column.from_arrow(ref.column(f.name), device="cpu", dtype=f.dtype).to_arrow().to_pylist()
         have = got[f.name].to_arrow().to_pylist()
         if f.dtype.kind == "float64":
-            assert all((a is None and b is None) or abs(a - b) <= 1e-12 * max(1, abs(b)) for a, b in zip(have, want)), f.name
+            # exact: the device parser is correctly rounded, like Arrow's
+            bits = lambda xs: [None if x is None else struct.pack("<d", x) for x in xs]
+            assert bits(have) == bits(want), f.name
         else:
             assert have == want, f.name
 
