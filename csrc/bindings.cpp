@@ -735,6 +735,36 @@ PYBIND11_MODULE(_native, m) {
   m.def("digest_hex", [](int algo, uintptr_t off, uintptr_t chars, int64_t n, uintptr_t out, uintptr_t s) {
     kern::digest_hex(algo, P<const int64_t>(off), P<const uint8_t>(chars), n, P<uint8_t>(out), S(s));
   });
+  m.def("bin_hex_encode", [](uintptr_t in, int64_t nbytes, uintptr_t out, uintptr_t s) {
+    kern::bin_hex_encode(P<const uint8_t>(in), nbytes, P<uint8_t>(out), S(s));
+  });
+  m.def("bin_hex_validate", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes, uintptr_t err,
+                               uintptr_t s) {
+    kern::bin_hex_validate(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
+                           P<int64_t>(err), S(s));
+  });
+  m.def("bin_hex_decode", [](uintptr_t off, int64_t n, uintptr_t in, int64_t nout, uintptr_t out, uintptr_t s) {
+    kern::bin_hex_decode(P<const int64_t>(off), n, P<const uint8_t>(in), nout, P<uint8_t>(out), S(s));
+  });
+  m.def("bin_b64_enc_lengths", [](uintptr_t off, uintptr_t valid, int64_t n, uintptr_t lens, uintptr_t s) {
+    kern::bin_b64_enc_lengths(P<const int64_t>(off), P<const uint8_t>(valid), n, P<int64_t>(lens), S(s));
+  });
+  m.def("bin_b64_dec_lengths", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes,
+                                  uintptr_t lens, uintptr_t err, uintptr_t s) {
+    kern::bin_b64_dec_lengths(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
+                              P<int64_t>(lens), P<int64_t>(err), S(s));
+  });
+  m.def("bin_b64_write", [](bool encode, uintptr_t ioff, uintptr_t chars, uintptr_t ooff, int64_t n,
+                            int64_t out_cap, uintptr_t out, uintptr_t s) {
+    kern::bin_b64_write(encode, P<const int64_t>(ioff), P<const uint8_t>(chars), P<const int64_t>(ooff), n,
+                        out_cap, P<uint8_t>(out), S(s));
+  });
+  m.def("utf8_num_tiles", &kern::utf8_num_tiles);
+  m.def("utf8_validate", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes, uintptr_t flags,
+                            uintptr_t err, uintptr_t s) {
+    kern::utf8_validate(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
+                        P<uint8_t>(flags), P<int64_t>(err), S(s));
+  });
   m.def("uuid_v4", [](uint64_t seed, int64_t n, uintptr_t out, uintptr_t s) {
     kern::uuid_v4(seed, n, P<uint8_t>(out), S(s));
   });

@@ -1,6 +1,7 @@
-// Cryptographic digests of string columns: md5, sha224, sha256, sha384,
-// sha512 (DataFusion's md5 / sha2 family / digest(), reference
-// Cargo.lock:1062-1090 datafusion-functions with md-5 and sha2).
+// Cryptographic digests of string / binary columns: md5, sha224, sha256,
+// sha384, sha512, blake2b, blake2s (DataFusion's md5 / sha2 family /
+// digest(), reference Cargo.lock:1062-1090 datafusion-functions with md-5,
+// sha2 and blake2).
 //
 // One lane per row: the lane walks its string in 64-byte (md5, sha-256) or
 // 128-byte (sha-512) blocks straight from HBM, applies the final padding
@@ -242,6 +243,99 @@ __device__ void sha512(const uint8_t* s, int64_t len, bool is384, uint64_t h[8])
   }
 }
 
+// ---------------------------------------------------------------- blake2b / blake2s
+// RFC 7693, unkeyed, full-length digests (64 / 32 bytes). One lane per row like the others: 128- /
+// 64-byte blocks straight from HBM, the last block zero-padded and compressed with the final flag,
+// the empty message one zero block with t = 0. The rounds are fully unrolled so the sigma
+// permutation indexes the sixteen message words at compile time (registers, no scratch).
+#define IGLOO_BLAKE_SIGMA                                                                           \
+  {{0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}, \
+   {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8}, \
+   {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9}, \
+   {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10}, \
+   {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}}
+
+template <class W, int kRounds, int kR1, int kR2, int kR3, int kR4>
+__device__ __forceinline__ void blake2_compress(W h[8], const W m[16], const W iv[8], uint64_t t, bool last) {
+  constexpr uint8_t sg[10][16] = IGLOO_BLAKE_SIGMA;
+  constexpr int kBits = 8 * (int)sizeof(W);
+  W v[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    v[i] = h[i];
+    v[8 + i] = iv[i];
+  }
+  v[12] ^= (W)t;
+  if (sizeof(W) == 4) v[13] ^= (W)(t >> 32);   // blake2b: the high counter word stays 0 (t < 2^64)
+  if (last) v[14] = ~v[14];
+#define IGLOO_ROTR(x, n) (((x) >> (n)) | ((x) << (kBits - (n))))
+#define IGLOO_G(a, b, c, d, x, y)                \
+  v[a] = v[a] + v[b] + (x);                      \
+  v[d] = IGLOO_ROTR((W)(v[d] ^ v[a]), kR1);      \
+  v[c] = v[c] + v[d];                            \
+  v[b] = IGLOO_ROTR((W)(v[b] ^ v[c]), kR2);      \
+  v[a] = v[a] + v[b] + (y);                      \
+  v[d] = IGLOO_ROTR((W)(v[d] ^ v[a]), kR3);      \
+  v[c] = v[c] + v[d];                            \
+  v[b] = IGLOO_ROTR((W)(v[b] ^ v[c]), kR4);
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    const uint8_t* q = sg[r % 10];
+    IGLOO_G(0, 4, 8, 12, m[q[0]], m[q[1]])
+    IGLOO_G(1, 5, 9, 13, m[q[2]], m[q[3]])
+    IGLOO_G(2, 6, 10, 14, m[q[4]], m[q[5]])
+    IGLOO_G(3, 7, 11, 15, m[q[6]], m[q[7]])
+    IGLOO_G(0, 5, 10, 15, m[q[8]], m[q[9]])
+    IGLOO_G(1, 6, 11, 12, m[q[10]], m[q[11]])
+    IGLOO_G(2, 7, 8, 13, m[q[12]], m[q[13]])
+    IGLOO_G(3, 4, 9, 14, m[q[14]], m[q[15]])
+  }
+#undef IGLOO_G
+#undef IGLOO_ROTR
+#pragma unroll
+  for (int i = 0; i < 8; ++i) h[i] ^= v[i] ^ v[8 + i];
+}
+
+// W = uint64_t: blake2b (128-byte blocks, 12 rounds); W = uint32_t: blake2s (64-byte blocks, 10 rounds)
+template <class W>
+__device__ void blake2(const uint8_t* s, int64_t len, W h[8]) {
+  constexpr int kW = (int)sizeof(W), kBlk = 16 * kW;
+  W iv[8];
+  if (kW == 8) {
+    const uint64_t c[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                           0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+    for (int i = 0; i < 8; ++i) iv[i] = (W)c[i];
+  } else {
+    const uint32_t c[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    for (int i = 0; i < 8; ++i) iv[i] = (W)c[i];
+  }
+  for (int i = 0; i < 8; ++i) h[i] = iv[i];
+  h[0] ^= (W)(0x01010000u | (unsigned)(8 * kW));      // digest length, no key, fanout = depth = 1
+  const int64_t nblocks = len == 0 ? 1 : (len + kBlk - 1) / kBlk;
+  for (int64_t blk = 0; blk < nblocks; ++blk) {
+    const int64_t b0 = blk * kBlk;
+    const bool last = blk == nblocks - 1;
+    W m[16];
+    if (b0 + kBlk <= len) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) __builtin_memcpy(&m[i], s + b0 + kW * i, kW);   // little-endian words
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        W x = 0;
+        for (int b = 0; b < kW; ++b) {
+          const int64_t k = b0 + kW * i + b;
+          if (k < len) x |= (W)s[k] << (8 * b);
+        }
+        m[i] = x;
+      }
+    }
+    const uint64_t t = (uint64_t)(last ? len : b0 + kBlk);
+    if (kW == 8) blake2_compress<W, 12, 32, 24, 16, 63>(h, m, iv, t, last);
+    else blake2_compress<W, 10, 16, 12, 8, 7>(h, m, iv, t, last);
+  }
+}
+
 __device__ __forceinline__ void put_hex(uint8_t* o, uint8_t v) {
   const char* hx = "0123456789abcdef";
   o[0] = (uint8_t)hx[v >> 4];
@@ -275,6 +369,23 @@ __global__ __launch_bounds__(kBlock) void digest_hex_kernel(int algo, const int6
       for (int i = 0; i < words; ++i)
         for (int k = 0; k < 8; ++k) put_hex(o + 16 * i + 2 * k, (uint8_t)(h[i] >> (56 - 8 * k)));
     }
+  }
+}
+
+// blake2 has a kernel of its own: its sixteen state plus sixteen message words would otherwise set
+// the register count (and the occupancy) of the md5 / sha kernel above.
+template <class W>
+__global__ __launch_bounds__(kBlock) void blake2_hex_kernel(const int64_t* __restrict__ off,
+                                                          const uint8_t* __restrict__ chars, int64_t n,
+                                                          uint8_t* __restrict__ out) {
+  constexpr int kW = (int)sizeof(W);
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = off[r], len = off[r + 1] - b;
+    W h[8];
+    blake2<W>(chars + b, len, h);
+    uint8_t* o = out + r * (int64_t)(16 * kW);
+    for (int i = 0; i < 8; ++i)
+      for (int k = 0; k < kW; ++k) put_hex(o + 2 * kW * i + 2 * k, (uint8_t)(h[i] >> (8 * k)));   // little-endian
   }
 }
 
@@ -318,6 +429,8 @@ int digest_width(int algo) {
     case kDigestSha256: return 64;
     case kDigestSha384: return 96;
     case kDigestSha512: return 128;
+    case kDigestBlake2b: return 128;
+    case kDigestBlake2s: return 64;
   }
   return -1;
 }
@@ -325,8 +438,10 @@ int digest_width(int algo) {
 void digest_hex(int algo, const int64_t* off, const uint8_t* chars, int64_t n, uint8_t* out, hipStream_t s) {
   if (digest_width(algo) < 0) throw std::runtime_error("digest: unknown algorithm");
   if (n == 0) return;
-  hipLaunchKernelGGL(digest_hex_kernel, dim3(grid_for(n, kBlock, 1 << 14)), dim3(kBlock), 0, s, algo, off, chars, n,
-                     out);
+  const dim3 g(grid_for(n, kBlock, 1 << 14));
+  if (algo == kDigestBlake2b) hipLaunchKernelGGL(blake2_hex_kernel<uint64_t>, g, dim3(kBlock), 0, s, off, chars, n, out);
+  else if (algo == kDigestBlake2s) hipLaunchKernelGGL(blake2_hex_kernel<uint32_t>, g, dim3(kBlock), 0, s, off, chars, n, out);
+  else hipLaunchKernelGGL(digest_hex_kernel, g, dim3(kBlock), 0, s, algo, off, chars, n, out);
   check_launch("digest_hex", s);
 }
 

@@ -414,7 +414,8 @@ void csv_str_copy(const int64_t* pos, const int64_t* len_flag, const int64_t* of
                   uint8_t* out, hipStream_t stream);
 
 // ---- digest.hip (md5 / sha2 hex digests of strings, uuid v4) --------------------
-enum DigestAlgo : int { kDigestMd5 = 0, kDigestSha224 = 1, kDigestSha256 = 2, kDigestSha384 = 3, kDigestSha512 = 4 };
+enum DigestAlgo : int { kDigestMd5 = 0, kDigestSha224 = 1, kDigestSha256 = 2, kDigestSha384 = 3, kDigestSha512 = 4,
+                        kDigestBlake2b = 5, kDigestBlake2s = 6 };
 int digest_width(int algo);   // hex characters per digest
 // out: n * digest_width(algo) bytes (row r at r * width)
 void digest_hex(int algo, const int64_t* off, const uint8_t* chars, int64_t n, uint8_t* out, hipStream_t s);
@@ -713,6 +714,24 @@ void str_levenshtein(const int64_t* oa, const uint8_t* ca, bool ba, const int64_
 // fills the -1 rows; scratch: lanes * cells int32, a row needs (shorter side + 1) <= cells
 void str_levenshtein_long(const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb,
                           int64_t n, int32_t* out, int32_t* scratch, int64_t lanes, int64_t cells, hipStream_t s);
+
+// ---- binary.hip (BINARY functions: hex / base64 encode and decode, UTF-8 validation) ----
+// err (int64[2], set to {n, 0} by the caller): [0] the smallest invalid row by atomicMin, [1] (hex) set
+// when a NULL row holds bytes. valid: one byte per row or null. Offsets need not start at 0.
+void bin_hex_encode(const uint8_t* in, int64_t nbytes, uint8_t* out, hipStream_t s);      // out: 2 * nbytes
+void bin_hex_validate(const int64_t* off, const uint8_t* chars, const uint8_t* valid, int64_t n, int64_t nbytes,
+                      int64_t* err, hipStream_t s);
+void bin_hex_decode(const int64_t* off, int64_t n, const uint8_t* in, int64_t nout, uint8_t* out, hipStream_t s);   // out: nout bytes
+void bin_b64_enc_lengths(const int64_t* off, const uint8_t* valid, int64_t n, int64_t* lens, hipStream_t s);
+void bin_b64_dec_lengths(const int64_t* off, const uint8_t* chars, const uint8_t* valid, int64_t n, int64_t nbytes,
+                         int64_t* lens, int64_t* err, hipStream_t s);
+// ooff: the scanned lengths; out: out_cap bytes, 8-byte aligned (nothing is written past out_cap)
+void bin_b64_write(bool encode, const int64_t* ioff, const uint8_t* chars, const int64_t* ooff, int64_t n,
+                   int64_t out_cap, uint8_t* out, hipStream_t s);
+int64_t utf8_num_tiles(int64_t nbytes);
+// flags: utf8_num_tiles(nbytes) bytes of scratch; nbytes: the size of chars
+void utf8_validate(const int64_t* off, const uint8_t* chars, const uint8_t* valid, int64_t n, int64_t nbytes,
+                   uint8_t* flags, int64_t* err, hipStream_t s);
 
 }  // namespace kern
 }  // namespace igloo

@@ -45,7 +45,7 @@ std::vector<NodeP> parse_sql(const std::string& text);
 
 // Token stream exposed for tests / tooling.
 struct Token {
-  enum Kind { Ident, QuotedIdent, Keyword, Number, String, Op, End } kind;
+  enum Kind { Ident, QuotedIdent, Keyword, Number, String, Bytes, Op, End } kind;   // Bytes: X'..', text = its hex digits
   std::string text;  // keywords upper-cased; identifiers lower-cased (unquoted)
   int pos;
 };

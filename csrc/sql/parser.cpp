@@ -62,6 +62,19 @@ std::vector<Token> tokenize(const std::string& t) {
       continue;
     }
     int start = (int)i;
+    if ((c == 'x' || c == 'X') && i + 1 < n && t[i + 1] == '\'') {  // X'0A0B' bytes literal
+      size_t j = t.find('\'', i + 2);
+      if (j == std::string::npos) throw ParseError("unterminated bytes literal", start);
+      std::string h = t.substr(i + 2, j - i - 2);
+      for (char d : h)
+        if (!std::isxdigit((unsigned char)d))
+          throw ParseError(std::string("bytes literal: '") + d + "' is not a hex digit at position " + std::to_string(start), start);
+      if (h.size() % 2)
+        throw ParseError("bytes literal needs an even number of hex digits at position " + std::to_string(start), start);
+      out.push_back({Token::Bytes, lower(h), start});
+      i = j + 1;
+      continue;
+    }
     if (std::isalpha((unsigned char)c) || c == '_') {
       size_t j = i;
       while (j < n && (std::isalnum((unsigned char)t[j]) || t[j] == '_' || t[j] == '$')) ++j;
@@ -1042,6 +1055,9 @@ class Parser {
       case Token::String:
         ++p_;
         return lit("str", t.text);
+      case Token::Bytes:
+        ++p_;
+        return lit("bytes", t.text);
       case Token::Op:
         if (t.text == "[") return arrayLiteral();
         if (t.text.size() > 1 && t.text[0] == '$') {  // $n parameter of a prepared statement

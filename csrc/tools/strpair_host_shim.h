@@ -1,7 +1,8 @@
 // Host stand-in for common.h: lets csrc/tools/strpair_host.cpp compile the device routines of
 // strpair.hip / strfunc.hip as plain C++ (one "thread" after another) under ASan / UBSan.
 // tests/test_strpair_host.py copies it next to copies of the two kernel files as common.h;
-// csrc/tools/textparse_host.cpp (tests/test_textparse_host.py) uses it the same way for textparse.h.
+// csrc/tools/textparse_host.cpp (tests/test_textparse_host.py) uses it the same way for textparse.h,
+// csrc/tools/binary_host.cpp (tests/test_binary_host.py) for binary.hip and digest.hip.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -22,6 +23,11 @@ typedef void* hipStream_t;
 #define hipLaunchKernelGGL(...) ((void)0)
 inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { auto o = *p; *p += v; return o; }
 inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) { auto o = *p; if (v > o) *p = v; return o; }
+inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) { auto o = *p; if (v < o) *p = v; return o; }
+// one "thread" after another: a barrier is a no-op, so kernels that share LDS run with blockDim.x == 1
+// (csrc/tools/binary_host.cpp) and a block-wide vote is this thread's own
+inline void __syncthreads() {}
+inline int __syncthreads_or(int p) { return p; }
 namespace igloo { namespace kern {
 constexpr int kWave = 64; constexpr int kBlock = 256;
 inline unsigned grid_for(int64_t n, int per, int64_t mx = 1 << 20) { return 1; }

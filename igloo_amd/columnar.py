@@ -26,7 +26,8 @@ class Column:
 
     * fixed width: ``data`` is a 1-D tensor (or [n, 2] int64 for int128 decimals);
     * plain UTF8: ``offsets`` int64 [n+1] and ``data`` uint8 bytes;
-    * dictionary UTF8: ``data`` int32 codes and ``dictionary`` a plain UTF8 Column.
+    * dictionary UTF8: ``data`` int32 codes and ``dictionary`` a plain UTF8 Column;
+    * BINARY: the plain UTF8 layout (a dictionary form only out of ``ops.strings.dict_encode``).
     ``valid`` is an optional bool tensor (True = not null).
     """
 
@@ -128,12 +129,16 @@ class Column:
         if dtype.is_nested:
             return Column.from_arrow(pa.array([value] * n, dtype.to_arrow()), device=device, dtype=dtype)
         if value is None:
-            if dtype.is_string:
+            if dtype.is_varlen:
                 return Column(dtype, torch.zeros(0, dtype=torch.uint8, device=device),
                               torch.zeros(n, dtype=torch.bool, device=device),
                               offsets=torch.zeros(n + 1, dtype=torch.int64, device=device))
             td = dtype.torch_dtype if dtype.kind != "null" else torch.bool
             return Column(dtype, torch.zeros(n, dtype=td, device=device), torch.zeros(n, dtype=torch.bool, device=device))
+        if dtype.is_binary:
+            b = bytes(value)
+            one = torch.tensor(list(b), dtype=torch.uint8).to(device)      # repeated on the device
+            return Column(dtype, one.repeat(n), offsets=torch.arange(n + 1, dtype=torch.int64, device=device) * len(b))
         if dtype.is_string:
             b = value.encode("utf-8")
             d = Column.from_arrow(pa.array([value], pa.large_string()), device=device)
@@ -182,22 +187,36 @@ class Column:
                 kids[fname] = Column.from_arrow(arr.field(i), device=device, dtype=ft, dict_encode=False)
             return Column(dtype, torch.arange(n, dtype=torch.int64, device=device), valid,
                           dictionary=Nested(children=kids))
+        if pa.types.is_dictionary(t) and dtype.is_binary:
+            arr = arr.cast(pa.large_binary())      # imported Binary is never dictionary-coded
+            t = arr.type
         if pa.types.is_dictionary(t):
             codes = np.array(arr.indices.cast(pa.int32()).fill_null(0).to_numpy(zero_copy_only=False))
             dic = Column.from_arrow(arr.dictionary.cast(pa.large_string()), device=device, dict_encode=False)
             return Column(T.UTF8, torch.from_numpy(codes.astype(np.int32)).to(device), valid, dictionary=dic)
-        if dtype.is_string:
-            arr = arr.cast(pa.large_string())
-            if dict_encode is None:
-                dict_encode = n >= 64 and _low_cardinality(arr)
-            if dict_encode:
-                return Column.from_arrow(pc.dictionary_encode(arr), device=device)
+        if dtype.is_varlen:
+            if dtype.is_binary:
+                if pa.types.is_fixed_size_binary(t) or pa.types.is_binary_view(t):
+                    arr = pa.array(arr.to_pylist(), pa.large_binary())
+                arr = arr.cast(pa.large_binary())
+                if dict_encode:
+                    # keys / ranks (ops.strings.dict_encode): codes over a plain Binary dictionary
+                    enc = pc.dictionary_encode(arr)
+                    codes = np.array(enc.indices.cast(pa.int32()).fill_null(0).to_numpy(zero_copy_only=False))
+                    dic = Column.from_arrow(enc.dictionary, device=device, dtype=T.BINARY)
+                    return Column(T.BINARY, torch.from_numpy(codes.astype(np.int32)).to(device), valid, dictionary=dic)
+            else:
+                arr = arr.cast(pa.large_string())
+                if dict_encode is None:
+                    dict_encode = n >= 64 and _low_cardinality(arr)
+                if dict_encode:
+                    return Column.from_arrow(pc.dictionary_encode(arr), device=device)
             bufs = arr.buffers()
             off = np.frombuffer(bufs[1], dtype=np.int64, count=n + 1, offset=arr.offset * 8).copy()
             base = off[0]
             off -= base
             data = np.frombuffer(bufs[2], dtype=np.uint8, count=int(off[-1]), offset=int(base)) if bufs[2] is not None and off[-1] > 0 else np.zeros(0, np.uint8)
-            return Column(T.UTF8, torch.from_numpy(data.copy()).to(device), valid,
+            return Column(dtype, torch.from_numpy(data.copy()).to(device), valid,
                           offsets=torch.from_numpy(off).to(device))
         if dtype.kind == "null":
             return Column(T.NULL, torch.zeros(n, dtype=torch.bool, device=device), torch.zeros(n, dtype=torch.bool, device=device))
@@ -235,7 +254,8 @@ class Column:
         dt = self.dtype
         if dt.is_nested:
             return _nested_to_arrow(self, n, validity)
-        if dt.is_string:
+        if dt.is_varlen:
+            at = dt.to_arrow()
             if self.dictionary is not None and self.data.is_cuda and len(self.dictionary) > 2 * n + 1024:
                 # small slice of a big dictionary (e.g. top-k rows of a grouped
                 # result): decode on the device, ship only the referenced bytes
@@ -248,10 +268,10 @@ class Column:
                     idx = pa.array(codes, pa.int32(), mask=~self.valid.cpu().numpy())
                 else:
                     idx = pa.array(codes, pa.int32())
-                return pc.take(dic, idx) if n else pa.array([], pa.large_string())
+                return pc.take(dic, idx) if n else pa.array([], at)
             off = self.offsets.cpu().numpy().astype(np.int64)
             chars = self.data.cpu().numpy().astype(np.uint8)
-            return pa.Array.from_buffers(pa.large_string(), n, [validity, pa.py_buffer(off), pa.py_buffer(chars)])
+            return pa.Array.from_buffers(at, n, [validity, pa.py_buffer(off), pa.py_buffer(chars)])
         if dt.kind == "null":
             return pa.nulls(n)
         if dt.is_decimal:

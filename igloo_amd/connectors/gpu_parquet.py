@@ -127,7 +127,7 @@ def conversion(leaf: dict, dt: T.DataType) -> Optional[Tuple[str, int, int]]:
         if phys == PHYS["FLBA"] and 1 <= leaf["type_length"] <= 16:
             return ("flba", 8, 1)
         return None
-    if k == "utf8":
+    if k in ("utf8", "binary"):     # BYTE_ARRAY with or without a string annotation: the same page layout
         return ("copy", 0, 1) if phys == PHYS["BYTE_ARRAY"] else None
     return None
 
@@ -330,7 +330,7 @@ class GpuParquetReader:
                         scratch=ptr(scratch) + 4 * ci * max(n, 1), str_len=0, str_pos=0, codes=0, dict_len=0,
                         dict_pos=0, raw=ptr(raw), dec=ptr(dec), error=ptr(err))
             post = {"lay": lay, "valid": valid}
-            if dt.kind != "utf8":
+            if not dt.is_varlen:
                 data = torch.empty(n, dtype=torch.bool if dt.kind == "bool" else dt.torch_dtype, device=device)
                 spec["out"] = ptr(data)
                 post["data"] = data
@@ -366,13 +366,22 @@ class GpuParquetReader:
             if "data" in post:
                 out[name] = Column(dt, post["data"], valid)
             elif "codes" in post:
-                dictionary = _gather_strings(post["dpos"], post["dlen"], device, s)
+                dictionary = _gather_strings(post["dpos"], post["dlen"], device, s, dtype=dt)
+                if dt.is_binary:
+                    # Binary stays plain: the page codes gather the rows out of the chunk dictionaries
+                    from ..ops.gather import take
+                    codes = post["codes"][:n]
+                    if valid is not None:
+                        codes = torch.where(valid, codes, torch.full_like(codes, -1))
+                    out[name] = take(dictionary, codes, neg=valid is not None)
+                    out[name].valid = valid
+                    continue
                 from ..ops.strings import dict_encode
                 enc = dict_encode(dictionary)  # entries repeated across chunk dictionaries -> one code
                 codes = enc.data.index_select(0, post["codes"][:n].long()).to(torch.int32)
                 out[name] = Column(T.UTF8, codes, valid, dictionary=enc.dictionary)
             else:
-                out[name] = _gather_strings(post["spos"][:n], post["slen"][:n], device, s, valid)
+                out[name] = _gather_strings(post["spos"][:n], post["slen"][:n], device, s, valid, dtype=dt)
 
 
 def _upload(b: bytes, device) -> torch.Tensor:
@@ -381,16 +390,16 @@ def _upload(b: bytes, device) -> torch.Tensor:
     return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(device)
 
 
-def _gather_strings(pos: torch.Tensor, lens: torch.Tensor, device, s, valid=None) -> Column:
+def _gather_strings(pos: torch.Tensor, lens: torch.Tensor, device, s, valid=None, dtype=T.UTF8) -> Column:
     off, total = offsets_from_lengths(lens)
     chars = torch.empty(total, dtype=torch.uint8, device=device)
     if total:
         launch("pq_str_copy").pq_str_copy(ptr(pos), ptr(off), lens.numel(), ptr(chars), s)
-    return Column(T.UTF8, chars, valid, offsets=off)
+    return Column(dtype, chars, valid, offsets=off)
 
 
 def _empty_column(dt: T.DataType, device) -> Column:
-    if dt.is_string:
+    if dt.is_varlen:
         return Column(dt, torch.zeros(0, dtype=torch.uint8, device=device), None,
                       offsets=torch.zeros(1, dtype=torch.int64, device=device))
     return Column(dt, torch.zeros(0, dtype=torch.bool if dt.kind == "bool" else dt.torch_dtype, device=device))

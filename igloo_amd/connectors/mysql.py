@@ -189,7 +189,9 @@ class MySqlConnection:
                     s, p = lenenc_str(c, p)
                     parts.append(s)
                 p += 1  # length of fixed fields (0x0c)
-                _charset, _collen, ctype, _flags, dec = struct.unpack("<HIBHB", c[p:p + 10])
+                charset, _collen, ctype, _flags, dec = struct.unpack("<HIBHB", c[p:p + 10])
+                if charset == 63 and ctype in _BYTE_TYPES:
+                    ctype |= _BINARY_FLAG       # the binary pseudo-charset: BINARY / VARBINARY / BLOB
                 cols.append((parts[4].decode(), ctype, dec))
             eof = self._packet()  # EOF after column definitions
             rows = []
@@ -220,7 +222,16 @@ class MySqlConnection:
         self.sock.close()
 
 
+#: string / blob column types; with charset 63 they hold bytes, not text
+_BYTE_TYPES = (15, 249, 250, 251, 252, 253, 254)
+_BINARY_FLAG = 0x100
+
+
 def _col_type(ctype: int, dec: int) -> T.DataType:
+    if ctype & _BINARY_FLAG:
+        from ..utils.errors import NotSupported
+        raise NotSupported("the MySQL connector does not read Binary (BINARY / VARBINARY / BLOB) columns: "
+                           "select HEX(col) or TO_BASE64(col) in the source query and decode() it")
     if ctype in (0, 246):
         return T.DECIMAL(38, dec)
     return TYPES.get(ctype, T.UTF8)

@@ -41,6 +41,10 @@ OIDS = {16: T.BOOL, 20: T.INT64, 21: T.INT16, 23: T.INT32, 26: T.INT64, 700: T.F
 
 
 def _oid_type(oid: int, typmod: int) -> T.DataType:
+    if oid == 17:
+        from ..utils.errors import NotSupported
+        raise NotSupported("the Postgres connector does not read Binary (bytea) columns: select "
+                           "encode(col, 'hex') in the source query and decode() it")
     if oid == 1700:
         if typmod >= 4:
             tm = typmod - 4

@@ -21,6 +21,11 @@ def _bool(v: str) -> bool:
 
 def write_table(tab: pa.Table, path: str, fmt: str, opts: Dict[str, str]) -> None:
     fmt = fmt.upper()
+    if fmt in ("CSV", "JSON", "NDJSON"):
+        for f in tab.schema:
+            if pa.types.is_large_binary(f.type) or pa.types.is_binary(f.type):
+                raise NotSupported(f"COPY ... STORED AS {fmt}: column {f.name} is Binary (encode() it, or write "
+                                   "Parquet / Arrow, which keep the type)")
     if fmt == "PARQUET":
         import pyarrow.parquet as pq
         comp = opts.get("compression", opts.get("format.compression", "zstd")).lower()

@@ -613,7 +613,7 @@ class QueryEngine:
         new = {}
         for (ci, _), f in zip(exprs, fields):
             col = batch.columns[ci.cid].to(dev)
-            if col.dtype.is_string and col.is_dict:
+            if col.dtype.is_varlen and col.is_dict:
                 from .ops import strings as S
                 col = S.decode(col)
             old = src.columns[f.name]

@@ -100,7 +100,7 @@ class HashAggExec(ExecNode):
             return None
         if lit.value is None or not (lit.dtype.is_integer or lit.dtype.is_decimal or lit.dtype.is_float):
             return None
-        if any(a.func in ("min", "max") and a.arg is not None and a.arg.dtype.is_string for _, a in lg.aggs):
+        if any(a.func in ("min", "max") and a.arg is not None and a.arg.dtype.is_varlen for _, a in lg.aggs):
             return None
         # an unfiltered scan whose group key column is sorted (decided before
         # running anything, so every other aggregate path stays available)
@@ -117,7 +117,7 @@ class HashAggExec(ExecNode):
                 return None      # (alike on every rank: placements follow from plan and catalog)
         kc = raw.columns.get(gexpr.cid) if hasattr(raw, "columns") else None
         if kc is None or kc.valid is not None or kc.data.dtype not in (torch.int32, torch.int64) \
-                or kc.data.dim() != 1 or kc.dtype.is_string or raw.num_rows < SORTED_HAVING_MIN_ROWS \
+                or kc.data.dim() != 1 or kc.dtype.is_varlen or raw.num_rows < SORTED_HAVING_MIN_ROWS \
                 or not H.is_sorted(kc.data):
             return None
         b = child.finish(raw, ctx)
@@ -382,7 +382,7 @@ class HashAggExec(ExecNode):
                 return None
         rcol = raw.columns.get(rkey.cid)
         lcol = ev.column(lkey, lb)
-        if rcol is None or rcol.dtype.is_string or lcol.dtype.is_string or rcol.is_dict \
+        if rcol is None or rcol.dtype.is_varlen or lcol.dtype.is_varlen or rcol.is_dict \
                 or rcol.data.dtype not in (torch.int32, torch.int64) or lcol.data.dtype not in (torch.int32, torch.int64):
             return None
         if ctx.spmd:
@@ -696,7 +696,7 @@ def _late_group_keys(groups, b: "LateBatch", ctx, skip: Optional[set] = None):
     if any(c is None or c not in b.owner for c in cids):
         return None
     base = [b.parts[b.owner[c]][0].columns[c] for c in cids]
-    plain = [i for i, c in enumerate(base) if c.dtype.is_string and not c.is_dict]
+    plain = [i for i, c in enumerate(base) if c.dtype.is_varlen and not c.is_dict]
     others = [i for i in range(len(cids)) if i not in plain]
     if not plain or not others:
         return None
@@ -772,7 +772,7 @@ def _encode_groups(gcols: List[Column], ctx, fd: bool = False):
     direct-mapped integer group-by replaces seven encodings; its SPMD merge
     groups custkey, balance, nation and the customer row shipped instead of
     the strings (parallel/exchange.py _partial_by_rows) the same way."""
-    plain = [i for i, c in enumerate(gcols) if c.dtype.is_string and not c.is_dict]
+    plain = [i for i, c in enumerate(gcols) if c.dtype.is_varlen and not c.is_dict]
     others = [i for i in range(len(gcols)) if i not in plain]
     keys: Dict[int, torch.Tensor] = {}
     reps_src: List[Column] = list(gcols)
@@ -817,7 +817,7 @@ def _encode_groups(gcols: List[Column], ctx, fd: bool = False):
 
 
 def _empty_col(t, dev) -> Column:
-    if t.is_string:
+    if t.is_varlen:
         return Column(t, torch.zeros(0, dtype=torch.uint8, device=dev), None, offsets=torch.zeros(1, dtype=torch.int64, device=dev))
     return Column(t, torch.zeros(0, dtype=t.torch_dtype if t.kind != "null" else torch.bool, device=dev))
 
@@ -931,14 +931,14 @@ def _plan_agg(ci, a: AggCall, b: Batch, gid, ng, n, ctx, specs, finals):
             finals.append(fin)
         return
     if func in ("min", "max"):
-        if src.is_string:
+        if src.is_varlen:
             d = col if col.is_dict else S.dict_encode(col)
             ranks = S.sort_ranks(d)
             vals = d.dictionary
             i = add("min_int" if func == "min" else "max_int", ranks.contiguous(), valid)
             # map winning rank back to a dictionary code
             from ..ops.sort import argsort as _argsort
-            dranks = S.sort_ranks(Column(T.UTF8, torch.arange(len(vals), dtype=torch.int32, device=dev), None,
+            dranks = S.sort_ranks(Column(src, torch.arange(len(vals), dtype=torch.int32, device=dev), None,
                                          dictionary=vals))
             order = _argsort([(dranks, False, False, None)], dranks.numel(), dev)
 
@@ -947,7 +947,7 @@ def _plan_agg(ci, a: AggCall, b: Batch, gid, ng, n, ctx, specs, finals):
                 vv = null_if_empty(r, rk)
                 safe = rk.clamp(0, max(len(order) - 1, 0))
                 codes = gather_tensor(order, safe).to(torch.int32) if len(order) else safe.to(torch.int32)
-                return ci, Column(T.UTF8, codes, vv, dictionary=d.dictionary)
+                return ci, Column(src, codes, vv, dictionary=d.dictionary)
             finals.append(fin)
             return
         if src.is_float:
@@ -999,7 +999,7 @@ def _order_perm(order, b: Batch, n: int, ctx) -> torch.Tensor:
     ks = []
     for e, asc, nf in order:
         c = ctx.evaluator.column(e, b)
-        if c.dtype.is_string:
+        if c.dtype.is_varlen:
             v = S.sort_ranks(c)
         elif c.is_wide:
             v = _convert_tensor(c, T.FLOAT64)

@@ -179,7 +179,7 @@ def _device_scalar(col: Column, t):
     ``_NO_SCALAR`` (host conversion)."""
     d = col.data
     if not d.is_cuda or col.offsets is not None or col.dictionary is not None or t.kind in ("null", "timestamp") \
-            or t.is_string:
+            or t.is_varlen:
         return _NO_SCALAR
     if col.valid is not None and not to_host_int(col.valid[:1]):
         return None

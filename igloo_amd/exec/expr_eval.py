@@ -295,7 +295,7 @@ class Evaluator:
             import operator as o
             f = {"=": o.eq, "<>": o.ne, "<": o.lt, "<=": o.le, ">": o.gt, ">=": o.ge}[op]
             return Scalar(bool(f(l.value, r.value)), T.BOOL)
-        if lt.is_string or rt.is_string:
+        if lt.is_varlen or rt.is_varlen:
             return self._compare_strings(op, l, r, b)
         if isinstance(l, Scalar) and l.value is None or isinstance(r, Scalar) and r.value is None:
             return Scalar(None, T.BOOL)
@@ -327,7 +327,7 @@ class Evaluator:
                 l, r, op = r, l, flip
             if r.value is None:
                 return Scalar(None, T.BOOL)
-            return Column(T.BOOL, S.compare_const(l, op, str(r.value)), l.valid)
+            return Column(T.BOOL, S.compare_const(l, op, _text(r.value)), l.valid)
         # two string columns: compare through one shared dictionary
         if l.is_dict and r.is_dict and l.dictionary is r.dictionary and op in ("=", "<>"):
             out = l.data == r.data if op == "=" else l.data != r.data
@@ -372,6 +372,14 @@ class Evaluator:
         src = v.dtype
         if src == t:
             return v
+        if t.is_binary and src.is_string:
+            from ..ops import binary as BN
+            return BN.to_binary(v)           # the same buffers relabelled
+        if t.is_string and src.is_binary:
+            from ..ops import binary as BN
+            return BN.to_utf8(v)             # validated per row (binary.hip)
+        if src.is_binary or t.is_binary:
+            raise NotSupported(f"CAST({src} AS {t}): Binary casts only to and from Utf8")
         if t.is_string:
             if src.is_string:
                 return v
@@ -399,8 +407,8 @@ class Evaluator:
         for cond, val in e.whens:
             vals.append((self.mask(cond, b), self.eval(val, b)))
         els = self.eval(e.else_, b) if e.else_ is not None else Scalar(None, t)
-        if t.is_string:
-            return self._case_strings(vals, els, n, dev)
+        if t.is_varlen:
+            return self._case_strings(vals, els, n, dev, t)
         rep = t
         out_v, out_valid = _full_of(els, rep, n, dev)
         for m, v in reversed(vals):
@@ -412,7 +420,7 @@ class Evaluator:
                 out_valid = torch.where(m, xvv, ov)
         return Column(t, out_v.to(t.torch_dtype) if t.kind != "null" else out_v, out_valid)
 
-    def _case_strings(self, vals, els, n, dev) -> Column:
+    def _case_strings(self, vals, els, n, dev, t=T.UTF8) -> Column:
         branches = [v for _, v in vals] + [els]
         if all(isinstance(v, Scalar) for v in branches):
             lits = []
@@ -428,24 +436,25 @@ class Evaluator:
                 if valid is not None or v.value is None:
                     valid = torch.where(m, torch.full((n,), v.value is not None, dtype=torch.bool, device=dev),
                                         valid if valid is not None else torch.ones(n, dtype=torch.bool, device=dev))
-            dic = Column.from_arrow(pa.array(lits or [""], pa.large_string()), device=dev, dict_encode=False)
-            return Column(T.UTF8, codes, valid, dictionary=dic)
+            dic = Column.from_arrow(pa.array(lits or [b"" if t.is_binary else ""], t.to_arrow()), device=dev, dtype=t,
+                                    dict_encode=False)
+            return Column(t, codes, valid, dictionary=dic)
         # general case: the first matching WHEN picks its branch (else the
         # ELSE branch); one device string gather assembles the rows
         choice = torch.full((n,), len(vals), dtype=torch.int64, device=dev)
         for k in range(len(vals) - 1, -1, -1):
             choice = torch.where(vals[k][0], torch.full_like(choice, k), choice)
-        return S.select_rows([self._str_col(v, dev) for v in branches], choice, n)
+        return S.select_rows([self._str_col(v, dev, t) for v in branches], choice, n)
 
     @staticmethod
-    def _str_col(v, dev) -> Column:
-        """A string operand as a column (a scalar becomes a one-row constant;
-        NULL a one-row NULL)."""
+    def _str_col(v, dev, t=T.UTF8) -> Column:
+        """A string / byte-string operand as a column (a scalar becomes a
+        one-row constant; NULL a one-row NULL)."""
         if isinstance(v, Scalar):
             if v.value is None:
-                c = S.const_column("", dev)
-                return Column(T.UTF8, c.data, torch.zeros(1, dtype=torch.bool, device=dev), offsets=c.offsets)
-            return S.const_column(str(v.value), dev)
+                c = S.const_column(b"" if t.is_binary else "", dev)
+                return Column(t, c.data, torch.zeros(1, dtype=torch.bool, device=dev), offsets=c.offsets)
+            return S.const_column(_text(v.value), dev)
         return v
 
     def _InList(self, e: InList, b: Batch) -> Value:
@@ -462,8 +471,8 @@ class Evaluator:
             hit = any(x.value == v.value for x in e.values)
             return Scalar(hit != e.negated if v.value is not None else None, T.BOOL)
         vals = [x.value for x in e.values if x.value is not None]
-        if v.dtype.is_string:
-            m = S.in_list(v, [str(x) for x in vals])
+        if v.dtype.is_varlen:
+            m = S.in_list(v, [_text(x) for x in vals])
         else:
             t = v.dtype
             lits = torch.tensor([_convert_scalar(x, xx.dtype, t) for x, xx in zip(vals, [y for y in e.values if y.value is not None])],
@@ -495,6 +504,12 @@ class Evaluator:
             if isinstance(c, Scalar):
                 c = Column.full(c.value, e.args[0].dtype, b.num_rows, self.device(b))
             return DG.hex_digest(c, e.options[0]) if name == "hex_digest" else DG.to_char(c, e.options[0])
+        if name in ("bin_encode", "bin_decode", "byte_length"):
+            from ..ops import binary as BN
+            c = args[0]
+            if name == "byte_length":
+                return Column(T.INT32, BN.byte_length(c), c.valid)
+            return BN.encode(c, e.options[0]) if name == "bin_encode" else BN.decode(c, e.options[0])
         if name == "upper":
             return S.upper(args[0])
         if name == "lower":
@@ -805,7 +820,7 @@ class Evaluator:
         n = b.num_rows
         dev = self.device(b)
         t = e.dtype
-        if t.is_string:
+        if t.is_varlen:
             # first non-NULL argument per row, assembled by one device gather
             choice = torch.full((n,), len(args) - 1, dtype=torch.int64, device=dev)
             for k in range(len(args) - 2, -1, -1):
@@ -816,7 +831,7 @@ class Evaluator:
                     continue
                 ok = a.valid if a.valid is not None else torch.ones(n, dtype=torch.bool, device=dev)
                 choice = torch.where(ok, torch.full_like(choice, k), choice)
-            return S.select_rows([self._str_col(a, dev) for a in args], choice, n)
+            return S.select_rows([self._str_col(a, dev, t) for a in args], choice, n)
         out, valid = _full_of(args[-1], t, n, dev)
         for a in reversed(args[:-1]):
             x, xv = _full_of(a, t, n, dev)
@@ -961,7 +976,7 @@ def _host_value(c: Column, t: DataType):
     timestamps in microseconds, decimals unscaled)."""
     if c.valid is not None and not bool(c.valid.cpu()[0]):
         return None
-    if t.is_string or t.is_nested:
+    if t.is_varlen or t.is_nested:
         return c.to_arrow()[0].as_py()
     v = c.data.cpu()[0]
     if t.kind == "bool":
@@ -1119,4 +1134,9 @@ def _concat_strings(a: Column, b: Column) -> Column:
         va = a.valid if a.valid is not None else torch.ones(na, dtype=torch.bool, device=a.device)
         vb = b.valid if b.valid is not None else torch.ones(nb, dtype=torch.bool, device=b.device)
         valid = torch.cat([va, vb])
-    return Column(T.UTF8, chars, valid, offsets=off)
+    return Column(a.dtype, chars, valid, offsets=off)
+
+
+def _text(v):
+    """A varlen constant for the string kernels: bytes stay bytes (Binary), anything else its text."""
+    return v if isinstance(v, bytes) else str(v)

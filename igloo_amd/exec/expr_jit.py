@@ -155,7 +155,7 @@ class _Gen:
         return f"t{self.n}"
 
     def input(self, c: Column) -> int:
-        if c.is_wide or c.dtype.is_string or c.dtype.kind not in _STORE or c.data.dim() != 1:
+        if c.is_wide or c.dtype.is_varlen or c.dtype.kind not in _STORE or c.data.dim() != 1:
             raise Bail("input column type")
         if c.data.dtype != c.dtype.torch_dtype:
             raise Bail("input storage dtype")
@@ -239,14 +239,14 @@ class _Gen:
         t = e.dtype
         if t.kind == "null":
             return "0", "false", T.INT64
-        if t.is_string:
+        if t.is_varlen:
             raise Bail("string literal")
         return self._lit_value(e.value, t)
 
     def _SubqueryExpr(self, e: SubqueryExpr):
         if e.kind != "scalar" or self.ev.ctx is None:
             raise Bail("subquery")
-        if e.dtype.is_string:
+        if e.dtype.is_varlen:
             raise Bail("string subquery")
         return self._lit_value(self.ev.ctx.scalar_subquery(e), e.dtype)
 
@@ -330,7 +330,7 @@ class _Gen:
         r = self.emit(e.right)
         lt, rt = l[2], r[2]
         if op in ("=", "<>", "<", "<=", ">", ">="):
-            if lt.is_string or rt.is_string:
+            if lt.is_varlen or rt.is_varlen:
                 raise Bail("string compare")
             t = lt if lt == rt else T.common_numeric(lt, rt)
             rep = T.INT64 if t.kind in ("date32", "timestamp", "bool") else t
@@ -407,7 +407,7 @@ class _Gen:
         t = e.dtype
         v = self.emit(e.x)
         src = v[2]
-        if t.is_string or src.is_string or src.kind == "null":
+        if t.is_varlen or src.is_varlen or src.kind == "null":
             raise Bail("string / null cast")
         if src == t:
             return v
@@ -418,7 +418,7 @@ class _Gen:
 
     def _Case(self, e: Case):
         t = e.dtype
-        if t.is_string or t.kind == "null":
+        if t.is_varlen or t.kind == "null":
             raise Bail("string case")
         ct = _ct(t)
         arms = []
@@ -444,7 +444,7 @@ class _Gen:
 
     def _InList(self, e: InList):
         v, va, t = self.emit(e.x)
-        if t.is_string or t.kind == "null":
+        if t.is_varlen or t.kind == "null":
             raise Bail("string IN")
         from .expr_eval import _convert_scalar
         lits = [_convert_scalar(x.value, x.dtype, t) for x in e.values if x.value is not None]
@@ -457,7 +457,7 @@ class _Gen:
         name = e.name
         if name == "coalesce":
             t = e.dtype
-            if t.is_string or t.kind == "null":
+            if t.is_varlen or t.kind == "null":
                 raise Bail("string coalesce")
             args = [self.emit(a) for a in e.args]
             ct = _ct(t)
@@ -666,7 +666,7 @@ def evaluate(e: Expr, b: Batch, ev) -> object:
     not worth / not able to be generated; PENDING while it compiles."""
     if not (ENABLED and jit.enabled()) or isinstance(e, _SIMPLE) or b.num_rows == 0:
         return None
-    if e.dtype.is_string or e.dtype.kind not in _STORE:
+    if e.dtype.is_varlen or e.dtype.kind not in _STORE:
         return None
     if not isinstance(e, _ROOTS):
         return None
@@ -678,7 +678,7 @@ def evaluate(e: Expr, b: Batch, ev) -> object:
         if _DEBUG:
             print(f"[expr_jit] {e.sql()}: not generated ({why})", flush=True)
         return None
-    if not g.inputs or t.kind not in _STORE or t.is_string:
+    if not g.inputs or t.kind not in _STORE or t.is_varlen:
         return None          # constant folding is the evaluator's job
     out_t = t                # the evaluator's result type for this node
     src = _source(g, out_t, val, valid)

@@ -74,7 +74,7 @@ class Spec:
         self._has_or = False
 
     def col(self, c: Column) -> int:
-        if c.valid is not None or c.is_wide or (c.dtype.is_string and not c.is_dict):
+        if c.valid is not None or c.is_wide or (c.dtype.is_varlen and not c.is_dict):
             raise Bail("nullable / wide / plain-string column")
         x = narrow(c.data)
         if x.dtype in (torch.bool, torch.uint8):
@@ -220,7 +220,7 @@ class Spec:
             self._range(ci, op, code)
             return
         lt, rt = (cast_t or col.dtype), r.dtype
-        if lt.is_float or rt.is_float or lt.is_string or rt.is_string:
+        if lt.is_float or rt.is_float or lt.is_varlen or rt.is_varlen:
             raise Bail("float / string comparison")
         if lt.kind in ("date32", "timestamp", "bool") or rt.kind in ("date32", "timestamp", "bool"):
             self._range(ci, op, int(r.value))
@@ -377,7 +377,7 @@ def _factors(e: Expr, spec: Spec) -> Tuple[List[tuple], int, bool]:
             raise Bail("dictionary / float argument")
         return [(ci, 0, 1)], (col.dtype.scale if col.dtype.is_decimal else 0), False
     if isinstance(e, Lit):
-        if e.value is None or t.is_float or t.is_string:
+        if e.value is None or t.is_float or t.is_varlen:
             raise Bail("literal argument")
         return [(-1, int(e.value), 0)], (t.scale if t.is_decimal else 0), False
     if isinstance(e, Cast) and t.is_decimal and (e.x.dtype.is_decimal or e.x.dtype.is_integer):
@@ -494,7 +494,7 @@ def fused_scan_aggregate(groups, aggs, b: Batch, pred: Optional[Expr], ctx) -> O
                         raise Bail("count over a nullable argument")
                 plan.append((ci, a, None))
                 continue
-            if a.arg.dtype.is_float or a.arg.dtype.is_string:
+            if a.arg.dtype.is_float or a.arg.dtype.is_varlen:
                 raise Bail("float / string argument")
             fs, scale, chk = _factors(a.arg, spec)
             want = a.arg.dtype.scale if a.arg.dtype.is_decimal else 0

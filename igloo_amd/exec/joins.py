@@ -53,7 +53,7 @@ def key_tensors(lcols: Sequence[Column], rcols: Sequence[Column]):
 
 
 def _pair_key(a: Column, b: Column) -> Tuple[torch.Tensor, torch.Tensor]:
-    if a.dtype.is_string or b.dtype.is_string:
+    if a.dtype.is_varlen or b.dtype.is_varlen:
         if a.is_dict and b.is_dict and a.dictionary is b.dictionary:
             return a.data, b.data
         from .expr_eval import _concat_strings
@@ -86,7 +86,7 @@ def group_key_tensor(c: Column, narrow: bool = False) -> Tuple[torch.Tensor, Col
     ``narrow``: a NULL-free dictionary column keeps its int32 codes (local
     grouping, whose packing and group-id kernels read either width) instead
     of a widened copy; sketches and exchanged keys stay int64."""
-    if c.dtype.is_string:
+    if c.dtype.is_varlen:
         d = c if c.is_dict else S.dict_encode(c)
         nd = len(d.dictionary) if d.dictionary is not None else None
         if narrow and d.valid is None and d.data.dtype == torch.int32:
@@ -197,7 +197,7 @@ def push_key_filter(build: ExecNode, on, lb: Batch, ctx) -> None:
         if found is None:
             continue
         agg, gexpr = found
-        if a.dtype.is_string or gexpr.dtype.is_string:
+        if a.dtype.is_varlen or gexpr.dtype.is_varlen:
             continue
         lcol = ctx.evaluator.column(a, lb)
         if ctx.spmd and lb.dist != ("replicated",):
@@ -301,7 +301,7 @@ def _semi_index_scan(rnode, j, ctx):
     names = {c.cid: resolve(c.cid) for c in (chain[0].logical.schema if chain else rnode.logical.schema)}
     raw = rnode.peek_raw(ctx)
     rcol = raw.columns.get(names.get(re_.cid))
-    if rcol is None or rcol.valid is not None or rcol.dtype.is_string or raw.num_rows < SORTED_JOIN_MIN_ROWS \
+    if rcol is None or rcol.valid is not None or rcol.dtype.is_varlen or raw.num_rows < SORTED_JOIN_MIN_ROWS \
             or not getattr(rcol.data, "_igloo_resident", False) or not H.is_sorted(rcol.data):
         return None
     if j.residual is not None and any(c not in names or names[c] not in raw.columns
@@ -328,7 +328,7 @@ def _semi_index_then_filter(found, j, lb: Batch, ctx) -> Optional[Batch]:
     if le.cid not in lb.columns or n_l == 0 or n_l * 2 > n_r:
         return None
     lcol = ctx.evaluator.column(le, lb)
-    if lcol.dtype.is_string:
+    if lcol.dtype.is_varlen:
         return None
     pl, pr, lvalid, _ = key_tensors([lcol], [rcol])
     if pr is not rcol.data:
@@ -445,6 +445,10 @@ def grace_join(lb: Batch, rb: Batch, kind: str, on, residual, ctx, null_aware=Fa
     need = JOIN_MEM_FACTOR * (_batch_bytes(lb) + _batch_bytes(rb))
     if need <= ctx.budget or lb.num_rows == 0 or rb.num_rows == 0:
         return None
+    if any(c.dtype.is_binary for b in (lb, rb) for c in b.columns.values()):
+        from ..utils.errors import NotSupported
+        raise NotSupported("the partitioned join under the device budget does not carry Binary columns: raise "
+                           "device_budget_gb, or encode() the column")
     from ..parallel.exchange import partition_keys
     ev = ctx.evaluator
     if kind == "anti" and null_aware:
@@ -896,7 +900,7 @@ def concat_columns(cols: List[Column]) -> Column:
     if c0.dtype.is_nested:
         from ..ops import nested as NS
         return NS.concat(cols, valid)
-    if c0.dtype.is_string:
+    if c0.dtype.is_varlen:
         if all(c.is_dict and c.dictionary is c0.dictionary for c in cols):
             return Column(c0.dtype, torch.cat([c.data for c in cols]), valid, dictionary=c0.dictionary)
         plains = [S.decode(c) for c in cols]
@@ -905,7 +909,7 @@ def concat_columns(cols: List[Column]) -> Column:
             o = p.offsets if i == 0 else p.offsets[1:]
             offs.append(o + base)
             base += to_host_int(p.offsets[-1:])
-        return Column(T.UTF8, torch.cat([p.data for p in plains]), valid, offsets=torch.cat(offs))
+        return Column(c0.dtype, torch.cat([p.data for p in plains]), valid, offsets=torch.cat(offs))
     if any(c.is_wide for c in cols) and not all(c.is_wide for c in cols):
         cols = [c if c.is_wide else Column(c.dtype, torch.stack([c.data, c.data >> 63], 1), c.valid) for c in cols]
     return Column(c0.dtype, torch.cat([c.data for c in cols]), valid)

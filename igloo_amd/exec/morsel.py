@@ -42,6 +42,7 @@ from typing import List, Optional
 import torch
 
 from ..columnar import Batch
+from ..utils.errors import NotSupported
 
 #: a morsel's scanned bytes are at most budget / MORSEL_FRACTION
 MORSEL_FRACTION = 8
@@ -104,7 +105,7 @@ def scan_bytes(scan) -> int:
         except Exception:  # noqa: BLE001 - sources without field lookup
             width += 8
             continue
-        if t.is_string:
+        if t.is_varlen:
             width += STRING_ROW_BYTES
         else:
             width += max(1, getattr(t, "byte_width", None) or 8) + 1
@@ -122,7 +123,22 @@ def pick_stream_scan(agg, ctx):
         b = scan_bytes(n)
         if b > best_bytes and stream_path_ok(agg.children[0], n):
             best, best_bytes = n, b
+    if best is not None:
+        _no_binary(best.logical.source, best.column_names()[0], "a morsel pipeline under the device budget")
     return best
+
+
+def _no_binary(src, names, what: str) -> None:
+    """The budgeted paths (morsel streaming, spilled partial states, the
+    external sort) stage rows in host memory and are not extended to Binary."""
+    for name in names:
+        try:
+            t = src.field(name).dtype
+        except Exception:  # noqa: BLE001 - sources without field lookup
+            continue
+        if t.is_binary:
+            raise NotSupported(f"{what} does not carry Binary columns (column {name}): raise device_budget_gb, "
+                               "or encode() the column")
 
 
 #: morsels prepared ahead of the one being processed (0: serial)
@@ -587,7 +603,7 @@ def semi_aggregate(kind, on, residual, null_aware, left_cids, right_plan, right_
         if not (isinstance(r, BinOp) and r.op == "<>" and isinstance(r.left, ColRef) and isinstance(r.right, ColRef)):
             return None
         x, y = (r.left, r.right) if r.left.cid in left_cids else (r.right, r.left)
-        if x.cid not in left_cids or y.cid not in rcids or x.dtype.is_string or y.dtype.is_string:
+        if x.cid not in left_cids or y.cid not in rcids or x.dtype.is_varlen or y.dtype.is_varlen:
             return None
         if x.dtype != y.dtype or x.dtype.is_float:
             # MIN/MAX(y) are compared with x as raw values: decimals of
@@ -710,9 +726,13 @@ def external_sort(b: Batch, keys, fetch, ctx) -> Optional[Batch]:
     need = SORT_MEM_FACTOR * _batch_bytes(b)
     if need <= ctx.budget:
         return None
+    for k, c in b.columns.items():
+        if c.dtype.is_binary:
+            raise NotSupported("the external sort under the device budget does not carry Binary columns: raise "
+                               "device_budget_gb, or encode() the column")
     e, asc, nulls_first = keys[0]
     lead = ctx.evaluator.column(e, b)
-    if lead.dtype.is_string or lead.is_wide or lead.data.dim() != 1 or lead.dictionary is not None:
+    if lead.dtype.is_varlen or lead.is_wide or lead.data.dim() != 1 or lead.dictionary is not None:
         return None
     P = 2
     while need / P > ctx.budget / 2 and P < 4096:

@@ -349,7 +349,7 @@ def _column_from_values(vals, dtype, device) -> Column:
     if dtype.kind == "null":
         return Column.full(None, T.NULL, len(vals), device)
     return Column.from_arrow(pa.array(vals, dtype.to_arrow()), device=device, dtype=dtype,
-                             dict_encode=False if dtype.is_string else None)
+                             dict_encode=False if dtype.is_varlen else None)
 
 
 # ================================================================ filter / project

@@ -82,7 +82,7 @@ def sort_batch(b: Batch, keys, fetch, ctx) -> Batch:
         lead = []
         for e, asc, nf in keys:
             c = ev.column(e, b)
-            if c.dtype.is_string or c.is_wide or c.data.dim() != 1:
+            if c.dtype.is_varlen or c.is_wide or c.data.dim() != 1:
                 break
             lead.append((c.data, not asc, nf, c.valid))
         if lead and len(lead) < len(keys):
@@ -93,7 +93,7 @@ def sort_batch(b: Batch, keys, fetch, ctx) -> Batch:
     ks = []
     for e, asc, nf in keys:
         c = ev.column(e, b)
-        if c.dtype.is_string:
+        if c.dtype.is_varlen:
             v = S.sort_ranks(c)
         elif c.is_wide:
             v = _convert_tensor(c, T.FLOAT64)

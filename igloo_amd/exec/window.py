@@ -164,7 +164,7 @@ class _Sorted:
 
 
 def _sort_value(c: Column) -> torch.Tensor:
-    if c.dtype.is_string:
+    if c.dtype.is_varlen:
         return S.sort_ranks(c)
     if c.is_wide:
         return _convert_tensor(c, T.FLOAT64)
@@ -234,7 +234,7 @@ def _apply_spec(b: Batch, calls, ctx) -> Batch:
 
 
 def _empty(t, dev) -> Column:
-    if t.is_string:
+    if t.is_varlen:
         return Column(t, torch.zeros(0, dtype=torch.uint8, device=dev), None,
                       offsets=torch.zeros(1, dtype=torch.int64, device=dev))
     return Column(t, torch.zeros(0, dtype=t.torch_dtype if t.kind != "null" else torch.bool, device=dev))
@@ -277,8 +277,9 @@ def _fill_default(res: Column, oob: torch.Tensor, dflt, t, n, dev) -> Column:
     if isinstance(dflt, Scalar):
         if dflt.value is None:
             return res
-        if t.is_string:
-            const = S.const_column(str(dflt.value), dev)
+        if t.is_varlen:
+            from .expr_eval import _text
+            const = S.const_column(_text(dflt.value), dev)      # bytes stay bytes (Binary)
             src = res if res.valid is not None else Column(res.dtype, res.data, None, res.offsets, res.dictionary)
             return S.select_rows([src, const], oob.to(torch.int64), n)
         val = _convert_scalar(dflt.value, dflt.dtype, t)
@@ -375,7 +376,7 @@ def _aggregate(w: WindowCall, b: Batch, st: _Sorted, lo, hi, ctx) -> Column:
     if f == "count":
         return Column(T.INT64, counts())
     src = col.dtype
-    if src.is_string and f in ("min", "max"):
+    if src.is_varlen and f in ("min", "max"):
         return _string_minmax(w, col, valid, st, lo, hi, read, ctx)
     if f in ("sum", "avg") and (col.is_wide or (w.dtype.is_decimal and w.dtype.precision > 18)):
         # exact 128-bit sums: three limb sums (32 + 32 + signed high word)

@@ -52,7 +52,7 @@ def _fmt(dt: T.DataType) -> str:
     if dt.is_decimal:
         return f"d:{max(dt.precision, 1)},{dt.scale}"
     return {"int8": "c", "int16": "s", "int32": "i", "int64": "l", "uint8": "C", "float32": "f", "float64": "g",
-            "bool": "b", "date32": "tdD", "null": "n"}.get(k) or ("U" if dt.is_string else None) or \
+            "bool": "b", "date32": "tdD", "null": "n"}.get(k) or ("U" if dt.is_string else "Z" if dt.is_binary else None) or \
         _unsupported(dt)
 
 
@@ -76,15 +76,15 @@ def _column_specs(c: Column, name: str, nullable: bool) -> Tuple[tuple, tuple]:
     validity = addr(_bitmap(c.valid)) if c.valid is not None else 0
     null_count = -1 if c.valid is not None else 0      # -1: not computed (no device sync)
     dt = c.dtype
-    if dt.is_string and c.is_dict:
+    if dt.is_varlen and c.is_dict:
         d = c.dictionary
         dschema, darray = _column_specs(d if not d.is_dict else d, "", False)
         sch = ("i", name, nullable, [], dschema)
         arr = (n, null_count, [validity, addr(c.data.to(torch.int32))], [], darray, keep)
         return sch, arr
-    if dt.is_string:
+    if dt.is_varlen:
         off = c.offsets.to(torch.int64)
-        return ("U", name, nullable, [], None), (n, null_count, [validity, addr(off), addr(c.data)], [], None, keep)
+        return (_fmt(dt), name, nullable, [], None), (n, null_count, [validity, addr(off), addr(c.data)], [], None, keep)
     if dt.kind == "null":
         return ("n", name, True, [], None), (n, n, [], [], None, keep)
     if dt.kind == "bool":
@@ -125,8 +125,9 @@ class DeviceResult:
     def __getitem__(self, name: str) -> torch.Tensor:
         """The column's data tensor (fixed-width types: DLPack-exportable as is)."""
         c = self.columns[name]
-        if c.dtype.is_string and not c.is_dict:
-            raise TypeError(f"column {name!r} is a variable-width string column: use __arrow_c_device_array__")
+        if c.dtype.is_varlen and not c.is_dict:
+            raise TypeError(f"column {name!r} is a variable-width {'Binary' if c.dtype.is_binary else 'string'} column: "
+                            "use __arrow_c_device_array__")
         return c.data
 
     def to_dlpack(self, name: str):

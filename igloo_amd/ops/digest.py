@@ -1,11 +1,14 @@
-"""md5 / sha224 / sha256 / sha384 / sha512 / digest(), uuid() and to_char()
+"""md5 / sha224 / sha256 / sha384 / sha512 / blake2b / blake2s / digest(), uuid() and to_char()
 (csrc/kernels/digest.hip, csrc/kernels/strfmt.hip).
 
 Parity: DataFusion's crypto / datetime string functions (reference
-Cargo.lock:1062-1090 datafusion-functions with md-5 and sha2; chrono's
+Cargo.lock:1062-1090 datafusion-functions with md-5, sha2 and blake2; chrono's
 strftime for to_char). DataFusion returns Binary for sha224..sha512 and
 digest(); here every digest is the lowercase hex text (md5's type) -- the
-bytes a client would hex-encode, parity unpinned for the column type. On the
+bytes a client would hex-encode, parity unpinned for the column type; the raw
+bytes are ``decode(sha256(x), 'hex')``. The argument is Utf8 or Binary.
+digest(x, 'blake2b') is the 64-byte and 'blake2s' the 32-byte unkeyed digest
+(blake3 is not offered: nothing here could check it). On the
 CPU the host hashlib / strftime give the same values (the GPU tests compare
 the kernels against hashlib).
 """
@@ -23,8 +26,8 @@ from .. import types as T
 from ..columnar import Column
 from ._lib import is_gpu, launch, native, ptr, stream
 
-ALGOS = {"md5": 0, "sha224": 1, "sha256": 2, "sha384": 3, "sha512": 4}
-WIDTH = {"md5": 32, "sha224": 56, "sha256": 64, "sha384": 96, "sha512": 128}
+ALGOS = {"md5": 0, "sha224": 1, "sha256": 2, "sha384": 3, "sha512": 4, "blake2b": 5, "blake2s": 6}
+WIDTH = {"md5": 32, "sha224": 56, "sha256": 64, "sha384": 96, "sha512": 128, "blake2b": 128, "blake2s": 64}
 
 
 def _fixed_width(chars: torch.Tensor, n: int, w: int, valid) -> Column:
@@ -33,12 +36,12 @@ def _fixed_width(chars: torch.Tensor, n: int, w: int, valid) -> Column:
 
 
 def hex_digest(col: Column, algo: str) -> Column:
-    """Hex digest of every string of ``col`` (NULL stays NULL)."""
+    """Hex digest of every string / byte string of ``col`` (NULL stays NULL)."""
     from . import strings as S
     algo = algo.lower()
     if algo not in ALGOS:
         from ..utils.errors import PlanError
-        raise PlanError(f"digest(): unsupported algorithm '{algo}' (md5, sha224, sha256, sha384, sha512)")
+        raise PlanError(f"digest(): unsupported algorithm '{algo}' ({', '.join(ALGOS)})")
     w = WIDTH[algo]
     if col.is_dict:
         # each distinct value once, the codes pick the digests
@@ -50,7 +53,7 @@ def hex_digest(col: Column, algo: str) -> Column:
     n = len(col)
     if not is_gpu(col.data):
         vals = col.to_arrow().to_pylist()
-        out = [None if v is None else hashlib.new(algo, v.encode("utf-8")).hexdigest() for v in vals]
+        out = [None if v is None else hashlib.new(algo, v if isinstance(v, bytes) else v.encode("utf-8")).hexdigest() for v in vals]
         return Column.from_arrow(pa.array(out, pa.large_string()), device=col.device, dict_encode=False)
     col = S.decode(col) if not col.is_plain_string else col
     chars = torch.empty(max(n * w, 1), dtype=torch.uint8, device=col.device)[:n * w]

@@ -153,6 +153,11 @@ def _consts(key, build):
     return v
 
 
+def _b(value) -> bytes:
+    """A constant operand's bytes: Binary constants are bytes already."""
+    return value if isinstance(value, bytes) else value.encode("utf-8")
+
+
 def _with_valid(values: torch.Tensor, col: Column) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     return values, col.valid
 
@@ -205,17 +210,17 @@ def compare_const(col: Column, op: str, value: str) -> torch.Tensor:
             return _dict_lut_dev(col, ("cmp", op, value), lambda d: compare_const(d, op, value))
         import operator as o
         f = {"=": o.eq, "<>": o.ne, "<": o.lt, "<=": o.le, ">": o.gt, ">=": o.ge}[op]
-        vb = value.encode("utf-8")
-        return _lut_apply(col, lambda: [(v is not None and f(v.encode("utf-8"), vb)) for v in col.dict_values()],
+        vb = _b(value)
+        return _lut_apply(col, lambda: [(v is not None and f(_b(v), vb)) for v in col.dict_values()],
                           ("cmp", op, value)).to(torch.bool)
     n = len(col)
     if not is_gpu(col.data):
         arr = col.to_arrow()
         fn = {"=": pc.equal, "<>": pc.not_equal, "<": pc.less, "<=": pc.less_equal, ">": pc.greater,
               ">=": pc.greater_equal}[op]
-        r = fn(arr, pa.scalar(value, pa.large_string()))
+        r = fn(arr, pa.scalar(value, col.dtype.to_arrow()))
         return torch.from_numpy(r.fill_null(False).to_numpy(zero_copy_only=False).astype(np.bool_))
-    vb = value.encode("utf-8")
+    vb = _b(value)
     ct = _consts(("bytes", value, col.device), lambda: torch.tensor(list(vb) or [0], dtype=torch.uint8).to(col.device))
     out = torch.empty(n, dtype=torch.bool, device=col.device)
     launch("str_cmp_const").str_cmp_const(ptr(col.offsets), ptr(col.data), n, ptr(ct), len(vb), CMP_OPS[op], ptr(out),
@@ -233,11 +238,13 @@ def in_set(col: Column, values: Sequence[str], prefix_chars: Optional[int] = Non
         nch = len(v)
         if prefix_chars is not None and nch > prefix_chars:
             continue                     # longer than the substring: never equal
-        vals.append(v.encode("utf-8"))
+        vals.append(_b(v))
         modes.append(1 if prefix_chars is not None and nch == prefix_chars else 0)
     n = len(col)
     if not is_gpu(col.data):
         base = substr(col, 1, prefix_chars) if prefix_chars is not None else col
+        if col.dtype.is_binary:
+            return in_list(base, vals) if vals else torch.zeros(n, dtype=torch.bool)
         return in_list(base, [v.decode("utf-8") for v in vals]) if vals else torch.zeros(n, dtype=torch.bool)
     out = torch.empty(n, dtype=torch.bool, device=col.device)
     key = ("in_set", tuple(vals), tuple(modes), col.device)
@@ -373,13 +380,13 @@ def char_length(col: Column) -> torch.Tensor:
 
 def const_column(value: str, device) -> Column:
     """One-row plain string column (a constant operand broadcast by the kernels)."""
-    b = value.encode("utf-8")
+    b = _b(value)
     key = ("const_col", value, str(device))
     def build():
         return (torch.tensor(list(b) or [0], dtype=torch.uint8).to(device)[:len(b)],
                 torch.tensor([0, len(b)], dtype=torch.int64).to(device))
     chars, off = _consts(key, build)
-    return Column(T.UTF8, chars, None, offsets=off)
+    return Column(T.BINARY if isinstance(value, bytes) else T.UTF8, chars, None, offsets=off)
 
 
 def concat(a: Column, b: Column, n: Optional[int] = None) -> Column:
@@ -492,7 +499,7 @@ def select_rows(branches: Sequence[Column], choice: torch.Tensor, n: int) -> Col
     for br in branches:
         p = decode(br)
         if p.valid is None:
-            p = Column(T.UTF8, p.data, torch.ones(len(p), dtype=torch.bool, device=p.device), offsets=p.offsets)
+            p = Column(p.dtype, p.data, torch.ones(len(p), dtype=torch.bool, device=p.device), offsets=p.offsets)
         parts.append(p)
         base.append(pos)
         pos += len(p)
@@ -501,7 +508,7 @@ def select_rows(branches: Sequence[Column], choice: torch.Tensor, n: int) -> Col
     for p in parts[1:]:
         offs.append(p.offsets[1:] + shift)
         shift = shift + p.offsets[-1:]
-    allc = Column(T.UTF8, torch.cat([p.data for p in parts]), torch.cat([p.valid for p in parts]),
+    allc = Column(parts[0].dtype, torch.cat([p.data for p in parts]), torch.cat([p.valid for p in parts]),
                   offsets=torch.cat(offs))
     rows = torch.arange(n, dtype=torch.int64, device=choice.device)
     starts = device_ints(base, choice.device)
@@ -517,7 +524,8 @@ def hash64(col: Column) -> torch.Tensor:
     if not is_gpu(col.data):
         import xxhash
         vals = col.to_pylist()
-        return torch.tensor([(xxhash.xxh64_intdigest(v.encode()) - 2**63) if v is not None else 0 for v in vals],
+        return torch.tensor([(xxhash.xxh64_intdigest(v if isinstance(v, bytes) else v.encode()) - 2**63)
+                             if v is not None else 0 for v in vals],
                             dtype=torch.int64)
     out = torch.empty(n, dtype=torch.int64, device=col.device)
     launch("str_hash64").str_hash64(ptr(col.offsets), ptr(col.data), n, ptr(col.valid), ptr(out), stream(out))
@@ -539,13 +547,19 @@ def decode(col: Column) -> Column:
     return c
 
 
+def _host_dict_encode(col: Column) -> Column:
+    if col.dtype.is_binary:
+        return Column.from_arrow(col.to_arrow(), device=col.device, dtype=T.BINARY, dict_encode=True)
+    return Column.from_arrow(pc.dictionary_encode(col.to_arrow()), device=col.device)
+
+
 def dict_encode(col: Column) -> Column:
     """Plain column -> dictionary column (exact: hash collisions are verified)."""
     if col.is_dict:
         return col
     n = len(col)
     if not is_gpu(col.data):
-        return Column.from_arrow(pc.dictionary_encode(col.to_arrow()), device=col.device)
+        return _host_dict_encode(col)
     h = hash64(col)
     gid, g, rep = group_ids(h)
     # verify every row equals its group's representative (no 64-bit collision)
@@ -556,10 +570,10 @@ def dict_encode(col: Column) -> Column:
     launch("str_eq_rows").str_eq_rows(ptr(col.offsets), ptr(col.data), ptr(ai), ptr(col.offsets), ptr(col.data),
                                       ptr(ri), False, n, ptr(mism), stream(mism))
     if to_host_int(mism):
-        return Column.from_arrow(pc.dictionary_encode(col.to_arrow()), device=col.device)
+        return _host_dict_encode(col)
     dictionary = take(col, rep)
     dictionary.valid = None
-    return Column(T.UTF8, gid, col.valid, dictionary=dictionary)
+    return Column(col.dtype, gid, col.valid, dictionary=dictionary)
 
 
 def sort_ranks(col: Column) -> torch.Tensor:
@@ -599,7 +613,12 @@ def _device_ranks(d: Column) -> torch.Tensor:
     chunks = max(1, (to_host_int(lens.max()) + 7) // 8)
     keys = torch.empty(chunks * n, dtype=torch.int64, device=dev)
     launch("str_prefix_keys").str_prefix_keys(ptr(d.offsets), ptr(d.data), n, chunks, ptr(keys), stream(keys))
-    perm = argsort([(keys[k * n:(k + 1) * n], False, False, None) for k in range(chunks)], n, dev)
+    cols = [(keys[k * n:(k + 1) * n], False, False, None) for k in range(chunks)]
+    if d.dtype.is_binary:
+        # the chunks are zero-padded, so x'61', x'6100' and x'610000' share their keys: the length
+        # is the least significant key (a shorter prefix sorts first). Text never ends in NUL bytes.
+        cols.append((lens.contiguous(), False, False, None))
+    perm = argsort(cols, n, dev)
     rank = torch.empty(n, dtype=torch.int64, device=dev)
     rank.index_copy_(0, perm.long(), torch.arange(n, dtype=torch.int64, device=dev))
     return rank

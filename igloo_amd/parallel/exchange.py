@@ -95,7 +95,7 @@ def with_dist(b: Batch, d) -> Batch:
 def partition_keys(c: Column) -> torch.Tensor:
     """Int64 per row whose mix64 decides the destination; identical for equal
     SQL values whatever the column representation (plain / dictionary)."""
-    if c.dtype.is_string:
+    if c.dtype.is_varlen:
         if c.is_dict:
             dh = S.hash64(c.dictionary)
             k = gather_tensor(dh, c.data)
@@ -176,15 +176,15 @@ def unify_dictionaries(cols: List[Column], comm, digests=None) -> List[Column]:
         c = cols[i]
         d = c.dictionary
         # same structure on every rank for the packed gather: plain, no validity
-        mine = Column(T.UTF8, d.data, None, offsets=d.offsets) if d.is_plain_string else \
-            Column(T.UTF8, S.decode(d).data, None, offsets=S.decode(d).offsets)
+        mine = Column(c.dtype, d.data, None, offsets=d.offsets) if d.is_plain_string else \
+            Column(c.dtype, S.decode(d).data, None, offsets=S.decode(d).offsets)
         counts = [x[0] for x in comm.allgather_ints([len(mine)])]
         every = _gather_column(mine, counts, comm)      # concatenation of all ranks' dictionaries
         enc = S.dict_encode(every)                      # union: codes into a deduplicated dictionary
         start = sum(counts[:comm.rank])
         remap = enc.data[start:start + len(mine)].to(torch.int32)
         codes = gather_tensor(remap, c.data) if len(mine) else c.data
-        out[i] = Column(T.UTF8, codes, c.valid, dictionary=enc.dictionary)
+        out[i] = Column(c.dtype, codes, c.valid, dictionary=enc.dictionary)
     return out
 
 
@@ -319,7 +319,7 @@ class ShufflePlan:
             for k in range(len(self.sgath)):
                 o = offs[k * (W + 1):(k + 1) * (W + 1)]
                 self.sbytes.append([o[r + 1] - o[r] for r in range(W)])
-        self.str_cols = [j for j, c in enumerate(cols) if c.dtype.is_string]
+        self.str_cols = [j for j, c in enumerate(cols) if c.dtype.is_varlen]
         self.rmat: Optional[List[List[int]]] = None
         self.full_max: Optional[int] = None
 
@@ -338,7 +338,7 @@ class ShufflePlan:
 
     @staticmethod
     def width(b: Batch, W: int) -> int:
-        return W * (1 + sum(1 for c in b.columns.values() if c.dtype.is_string))
+        return W * (1 + sum(1 for c in b.columns.values() if c.dtype.is_varlen))
 
     def receive(self, pre: List[List[int]], rank: int, nb: Batch) -> bool:
         """The count matrix from every rank's ``preamble`` (``pre[r]``);
@@ -675,7 +675,7 @@ def gather_small(b: Batch, ctx, cap_rows: int) -> Batch:
             anyf |= h[2 + j]
         valid = parts[t] if anyf & 1 else None
         t += 1
-        if c0.dtype.is_string:
+        if c0.dtype.is_varlen:
             lens = parts[t]
             t += 1
             base = H + cap_rows * rb + sc * cap_s
@@ -795,7 +795,7 @@ def prepare_join(lb: Batch, rb: Batch, join: L.Join, ctx, rows: Optional[Tuple[i
     ev = ctx.evaluator
     le, re_ = on[0]
     lcol, rcol = ev.column(le, lb), ev.column(re_, rb)
-    if lcol.dtype.is_string or rcol.dtype.is_string:
+    if lcol.dtype.is_varlen or rcol.dtype.is_varlen:
         lk, rk = partition_keys(lcol), partition_keys(rcol)
     else:
         lk, rk = _pair_key(lcol, rcol)
@@ -840,7 +840,7 @@ def semi_by_key_set(lb: Batch, rb: Batch, join: L.Join, ctx) -> Optional[Batch]:
     ev = ctx.evaluator
     le, re_ = join.on[0]
     lcol, rcol = ev.column(le, lb), ev.column(re_, rb)
-    if lcol.dtype.is_string or rcol.dtype.is_string or lcol.data.dim() != 1 or rcol.data.dim() != 1 \
+    if lcol.dtype.is_varlen or rcol.dtype.is_varlen or lcol.data.dim() != 1 or rcol.data.dim() != 1 \
             or not (lcol.dtype.is_integer or lcol.dtype.kind == "date32") \
             or not (rcol.dtype.is_integer or rcol.dtype.kind == "date32"):
         return None
@@ -884,7 +884,7 @@ def _semi_by_range_marks(lb: Batch, rb: Batch, join: L.Join, ctx) -> Optional[Ba
     ev = ctx.evaluator
     lcol, rcol = ev.column(le, lb), ev.column(re_, rb)
     for c in (lcol, rcol):
-        if c.dtype.is_string or c.data.dim() != 1 or not (c.dtype.is_integer or c.dtype.kind == "date32") \
+        if c.dtype.is_varlen or c.data.dim() != 1 or not (c.dtype.is_integer or c.dtype.kind == "date32") \
                 or c.dtype.is_decimal:
             return None
     dev = ctx.device
@@ -996,7 +996,7 @@ def distributed_aggregate(lg: L.Aggregate, b: Batch, ctx, local=None) -> Batch:
         pm = materialized(pb)
         extra = _int_key_ranges(groups, pm) if dense_plan else []
         nr = len(extra)
-        strs = [k for k, c in pm.columns.items() if c.dtype.is_string]
+        strs = [k for k, c in pm.columns.items() if c.dtype.is_varlen]
         extra += [pm.num_rows] + [_str_bytes(pm.columns[k]) if pm.columns[k].is_plain_string else -1 for k in strs]
         # a shuffle plan travels with the preamble when this rank already
         # knows the dense domain is too large (its local ranges exceed it)
@@ -1126,18 +1126,18 @@ def _shuffle_key(groups, b: Batch):
 def _dense_candidate(groups, partial) -> bool:
     """Plan-level part of the dense all-reduce test (alike on every rank)."""
     for _, a in partial:
-        if a.func not in ("sum", "count", "min", "max", "bool_and", "bool_or") or a.dtype.is_string:
+        if a.func not in ("sum", "count", "min", "max", "bool_and", "bool_or") or a.dtype.is_varlen:
             return False
     for ci, _ in groups:
         t = ci.dtype
-        if not (t.is_string or t.kind == "bool" or t.kind == "date32" or (t.is_integer and not t.is_decimal)):
+        if not (t.is_varlen or t.kind == "bool" or t.kind == "date32" or (t.is_integer and not t.is_decimal)):
             return False
     return True
 
 
 def _is_int_key(ci) -> bool:
     t = ci.dtype
-    return not t.is_string and t.kind != "bool" and (t.kind == "date32" or t.is_integer)
+    return not t.is_varlen and t.kind != "bool" and (t.kind == "date32" or t.is_integer)
 
 
 def _int_key_ranges(groups, pb: Batch) -> List[int]:
@@ -1170,7 +1170,7 @@ def _local_domain(groups, pb: Batch, ranges: List[int]) -> int:
             lo, hi = ranges[ri], ranges[ri + 1]
             ri += 2
             span = hi - lo + 1 if lo <= hi else 1
-        elif c.dtype.is_string and not c.is_dict:
+        elif c.dtype.is_varlen and not c.is_dict:
             return DENSE_ALLREDUCE_MAX + 1
         else:
             span = len(c.dictionary) if c.is_dict else 2
@@ -1315,7 +1315,7 @@ def _dense_allreduce(groups, partial, pb: Batch, ctx) -> Optional[Batch]:
     dev = ctx.device
     cols = [pb.columns[ci.cid] for ci, _ in partial]
     keys = [pb.columns[ci.cid] for ci, _ in groups]
-    if any(k.dtype.is_string and not k.is_dict for k in keys):
+    if any(k.dtype.is_varlen and not k.is_dict for k in keys):
         return None
     ranges = [list(r) for r in pb.preamble]
     sizes, offs, ri = [], [], 0

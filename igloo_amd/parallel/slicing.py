@@ -243,7 +243,7 @@ def slice_columns(cols: Dict[str, Column], n: int, key: str, world: int, rank: i
     plan = memo.get(("bounds", world, rank))
     if plan is None:
         with unlogged():    # remembered on the resident key tensor: a one-time cost
-            if kc is not None and kc.valid is None and kt.dim() == 1 and not kc.dtype.is_string \
+            if kc is not None and kc.valid is None and kt.dim() == 1 and not kc.dtype.is_varlen \
                     and kt.dtype in (torch.int32, torch.int64) and n and H.is_sorted(kt):
                 kmin, kmax = to_host_ints(kt[[0, -1]].to(torch.int64))
                 chunk = range_chunk(kmin, kmax, world)

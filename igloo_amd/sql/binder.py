@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 from .. import types as T
 from . import template as TPL
 from ..types import BOOL, DATE32, FLOAT64, INT32, INT64, UTF8, DataType
-from ..utils.errors import NotSupported, PlanError, TableNotFound
+from ..utils.errors import ExecutionError, NotSupported, PlanError, TableNotFound
 from .expr import (AGG_FUNCS, FRAME_KINDS, RANKING_FUNCS, VALUE_FUNCS, AggCall, BinOp, Case, Cast, ColRef, Expr,
                    Func, InList, IsNull, Like, Lit, Neg, Not, SubqueryExpr, WindowCall, WindowFrame, and_all, col_refs,
                    transform, walk)
@@ -740,6 +740,8 @@ class Binder:
                     both = l.dtype.kind == r.dtype.kind
                     return self._nested_func("array_concat" if both else
                                              "array_append" if l.dtype.kind == "list" else "array_prepend", [l, r])
+                if l.dtype.is_binary or r.dtype.is_binary:
+                    raise NotSupported("|| on Binary operands (cast to VARCHAR first)")
                 return Func("concat", [self._coerce(l, UTF8), self._coerce(r, UTF8)], UTF8)
             if op in ("~", "~*", "!~", "!~*"):
                 # POSIX regex match operators: regexp_like, '*' = case-insensitive
@@ -774,6 +776,8 @@ class Binder:
                     e = BinOp("or", e, o, BOOL)
                 return Not(e) if node.get("neg") else e
             t = x.dtype
+            for v in vals:
+                _no_binary_vs_utf8(t, v.dtype, "IN list")
             vals = [self._coerce_lit(v, t) for v in vals]
             return InList(x, vals, bool(node.get("neg")))
         if k == "like":
@@ -784,6 +788,8 @@ class Binder:
             esc = "\\"
             if node.get("escape"):
                 esc = self.bind_expr(node["escape"], scope).value
+            if x.dtype.is_binary:
+                raise NotSupported("LIKE / ILIKE on a Binary operand (CAST it to VARCHAR, or encode() it)")
             e = Like(self._coerce(x, UTF8), TPL.peek(p), bool(node.get("neg")), bool(node.get("ilike")), esc)
             TPL.raw(e, "pattern", lambda a: a.value, p)      # (a template re-reads the pattern)
             return e
@@ -800,6 +806,8 @@ class Binder:
             i = int(node["s"]) - 1
             if not 0 <= i < len(params):
                 raise PlanError(f"no value for parameter ${i + 1} ({len(params)} given)")
+            if params[i].dtype.is_binary or isinstance(getattr(params[i], "value", None), (bytes, bytearray)):
+                raise NotSupported(f"parameter ${i + 1} of type Binary: write the value as an X'..' literal")
             return params[i]
         if k == "isnull":
             x = self.bind_expr(node["c"][0], scope, allow_agg)
@@ -834,6 +842,7 @@ class Binder:
             x = self.bind_expr(node["c"][0], scope, allow_agg)
             if len(bq.plan.schema) != 1:
                 raise PlanError("IN subquery must return exactly one column")
+            _no_binary_vs_utf8(x.dtype, bq.plan.schema[0].dtype, "IN (subquery)")
             return SubqueryExpr("in", bq.plan, x, bool(node.get("neg")), BOOL, outer)
         if k == "row":
             raise NotSupported("row constructors")
@@ -867,6 +876,8 @@ class Binder:
             return Lit(float(s), FLOAT64)
         if t == "str":
             return Lit(s, UTF8)
+        if t == "bytes":
+            return Lit(bytes.fromhex(s), T.BINARY)      # X'0a0b': the lexer checked the digits
         if t == "bool":
             return Lit(s == "true", BOOL)
         if t == "null":
@@ -917,6 +928,7 @@ class Binder:
     def _cmp(self, op: str, l: Expr, r: Expr) -> Expr:
         lt, rt = l.dtype, r.dtype
         _no_map_keys([l, r], f"comparison ({op})")
+        _no_binary_vs_utf8(lt, rt, f"comparison ({op})")
         # literal coercion towards the column type
         if lt != rt:
             if isinstance(r, Lit) and not isinstance(l, Lit):
@@ -985,7 +997,7 @@ class Binder:
             if op == "+" and rt.kind == "date32" and lt.is_integer:
                 return _fold(BinOp(op, r, l, DATE32))
             raise PlanError(f"cannot apply {op} to {lt} and {rt}")
-        if lt.is_string or rt.is_string:
+        if lt.is_varlen or rt.is_varlen:
             raise PlanError(f"cannot apply {op} to {lt} and {rt}")
         if lt.kind == "null" or rt.kind == "null":
             t = rt if lt.kind == "null" else lt
@@ -1110,6 +1122,10 @@ class Binder:
                 order = ()      # ORDER BY does not change an order-insensitive aggregate
             return _make_agg(name, arg, distinct, flt, arg2, param, order)
         args = [self.bind_expr(a, scope, allow_agg) for a in node["c"]]
+        if any(a.dtype.is_binary for a in args):
+            return self._binary_func(name, args)
+        if name in ("encode", "decode"):
+            return self._encode_decode(name, args)
         if name in ("upper", "lower", "capitalize"):
             _nargs(name, args, 1)
             a = self._coerce(args[0], UTF8)
@@ -1184,7 +1200,7 @@ class Binder:
                 if len(args) != 2 or not isinstance(args[1], Lit) or not isinstance(args[1].value, str):
                     raise PlanError("digest(value, algorithm): the algorithm must be a string constant")
                 algo = args[1].value.lower()
-                if algo not in ("md5", "sha224", "sha256", "sha384", "sha512"):
+                if algo not in _DIGESTS:
                     raise NotSupported(f"digest(): algorithm '{algo}'")
             else:
                 _nargs(name, args, 1)
@@ -1537,6 +1553,70 @@ class Binder:
             return Lit(None if x.value is None else _date_part_py(x.value, field), INT32)
         return Func("date_part", [x], INT32, (field,))
 
+    # ------------------------------------------------------ Binary functions
+    def _encode_decode(self, name: str, args: List[Expr]) -> Expr:
+        """encode(x, fmt) -> Utf8, decode(x, fmt) -> Binary (ops/binary.py); x Utf8 or Binary,
+        fmt a string constant 'hex' | 'base64' in any letter case. Literal arguments fold."""
+        from ..ops import binary as BN
+        _nargs(name, args, 2)
+        if not isinstance(args[1], Lit) or not isinstance(args[1].value, str):
+            raise PlanError(f"{name}(value, format): the format must be a string constant ('hex', 'base64')")
+        fmt = BN.check_format(args[1].value, name)
+        a = args[0] if args[0].dtype.is_binary else self._coerce(args[0], UTF8)
+        rt = UTF8 if name == "encode" else T.BINARY
+        if isinstance(a, Lit):
+            v = a.value
+            if v is None:
+                return Lit(None, rt)
+            v = v if isinstance(v, bytes) else v.encode("utf-8")
+            if name == "encode":
+                return Lit(BN.py_encode(v, fmt), rt)
+            try:
+                return Lit(BN.py_decode(v, fmt), rt)
+            except ValueError as e:
+                raise ExecutionError(f"decode(): invalid {fmt} input {a.sql()}: {e}") from None
+        return Func("bin_encode" if name == "encode" else "bin_decode", [a], rt, (fmt,))
+
+    def _binary_func(self, name: str, args: List[Expr]) -> Expr:
+        """A function call with a Binary argument: only what moves, measures,
+        encodes or hashes bytes is offered; the text functions would need a cast."""
+        if name in ("encode", "decode"):
+            return self._encode_decode(name, args)
+        if name in ("coalesce", "ifnull", "nvl"):
+            if any(not (a.dtype.is_binary or a.dtype.kind == "null") for a in args):
+                raise PlanError(f"{name}(): Binary and {[a.dtype for a in args if not a.dtype.is_binary][0]} arguments")
+            return Func("coalesce", [self._coerce(a, T.BINARY) for a in args], T.BINARY)
+        if name == "nullif":
+            _nargs(name, args, 2)
+            return Case([(self._cmp("=", args[0], args[1]), Lit(None, args[0].dtype))], args[0], args[0].dtype)
+        if name == "arrow_typeof":
+            _nargs(name, args, 1)
+            return Lit(arrow_type_name(args[0].dtype), UTF8)
+        if name in ("length", "octet_length", "bit_length"):
+            _nargs(name, args, 1)
+            a = args[0]
+            n = Lit(None if a.value is None else len(a.value), INT32) if isinstance(a, Lit) else \
+                Func("byte_length", [a], INT32)
+            return n if name != "bit_length" else _fold(BinOp("*", self._cast(n, INT64), Lit(8, INT64), INT64))
+        if name in ("md5", "sha224", "sha256", "sha384", "sha512", "digest"):
+            if name == "digest":
+                if len(args) != 2 or not isinstance(args[1], Lit) or not isinstance(args[1].value, str):
+                    raise PlanError("digest(value, algorithm): the algorithm must be a string constant")
+                algo = args[1].value.lower()
+                if algo not in _DIGESTS:
+                    raise NotSupported(f"digest(): algorithm '{algo}'")
+            else:
+                _nargs(name, args, 1)
+                algo = name
+            a = args[0] if args[0].dtype.is_binary else self._coerce(args[0], UTF8)
+            if isinstance(a, Lit):
+                import hashlib
+                v = a.value
+                return Lit(None if v is None else hashlib.new(algo, v if isinstance(v, bytes) else v.encode()).hexdigest(),
+                           UTF8)
+            return Func("hex_digest", [a], UTF8, (algo,))
+        raise NotSupported(f"{name}() on a Binary argument (CAST it to VARCHAR, or encode() it)")
+
     # ------------------------------------------------------ function library
     def _func_library(self, name: str, args: List[Expr]) -> Expr:
         """DataFusion built-ins beyond the TPC-H set (strings, math, dates)."""
@@ -1572,6 +1652,9 @@ class Binder:
         def per_row(i):
             # the call has exactly two arguments and the i-th is no string literal
             return len(args) == 2 and not (isinstance(args[i], Lit) and isinstance(args[i].value, str))
+        if any(a.dtype.is_binary for a in args):
+            # (reached without _func: the regex operators and SIMILAR TO)
+            raise NotSupported(f"{name}() on a Binary argument (CAST it to VARCHAR, or encode() it)")
         if not args and name not in ("pi", "random", "now", "current_timestamp", "current_date", "today",
                                      "uuid", "current_time"):
             raise PlanError(f"{name}() needs arguments")
@@ -1799,6 +1882,8 @@ class Binder:
                         raise NotSupported(f"{name}() default must be a literal")
                     if t.kind == "null":
                         t = args[2].dtype
+                    if t.is_binary != args[2].dtype.is_binary:
+                        raise PlanError(f"{name}(): a default of type {args[2].dtype} for a value of type {t}")
                     wargs.append(self._coerce(args[2], t))
                 return WindowCall("lag", wargs, part, order, frame, t, None, (k if name == "lag" else -k,))
             if name == "nth_value":
@@ -2247,6 +2332,14 @@ def _date_part_py(days: int, field: str) -> int:
             "dow": (d.weekday() + 1) % 7, "doy": d.timetuple().tm_yday, "week": d.isocalendar()[1]}[field]
 
 
+def _no_binary_vs_utf8(a: DataType, b: DataType, what: str) -> None:
+    if {a.kind, b.kind} == {"utf8", "binary"}:
+        raise PlanError(f"{what}: cannot compare {a} with {b}: CAST one side (bytes compare byte-wise, text is not bytes)")
+
+
+_DIGESTS = ("md5", "sha224", "sha256", "sha384", "sha512", "blake2b", "blake2s")
+
+
 def _fold_cast(v: Lit, t: DataType) -> Lit:
     if TPL.tracking(v):
         return TPL.derive(lambda a, t=t: _fold_cast(a, t), v)
@@ -2271,6 +2364,17 @@ def _fold_cast(v: Lit, t: DataType) -> Lit:
             if src.is_decimal:
                 return Lit(x / 10**src.scale, t)
             return Lit(float(x), t)
+        if t.is_binary:
+            if src.is_string:
+                return Lit(x.encode("utf-8"), t)
+            raise PlanError(f"cannot cast {v.sql()} ({src}) to {t}")
+        if src.is_binary:
+            if t.is_string:
+                try:
+                    return Lit(x.decode("utf-8"), t)
+                except UnicodeDecodeError:
+                    raise ExecutionError(f"CAST(Binary AS Utf8): {v.sql()} is not valid UTF-8") from None
+            raise PlanError(f"cannot cast {v.sql()} ({src}) to {t}")
         if t.is_string:
             if src.is_decimal:
                 return Lit(Lit(x, src).sql(), t)

@@ -66,6 +66,8 @@ class Lit(Expr):
             return f"DATE '{datetime.date(1970, 1, 1) + datetime.timedelta(days=self.value)}'"
         if isinstance(self.value, str):
             return "'" + self.value.replace("'", "''") + "'"
+        if isinstance(self.value, bytes):
+            return "X'" + self.value.hex() + "'"
         return str(self.value)
 
 

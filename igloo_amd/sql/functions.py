@@ -29,6 +29,8 @@ STRING: Dict[str, str] = {
     "levenshtein": "levenshtein(s, reverse(s))", "contains": "contains(s, 'ab')",
     "find_in_set": "find_in_set(s, 'abc,caba')", "substr_index": "substr_index(s, ' ', 2)",
     "substring_index": "substring_index(s, 'b', -1)",
+    # Binary (ops/binary.py): base64 is unpadded, parity unpinned
+    "encode": "encode(s, 'base64')", "decode": "decode(encode(s, 'hex'), 'hex')",
 }
 NUMERIC: Dict[str, str] = {
     "abs": "abs(n - 3)", "round": "round(f, 1)", "ceil": "ceil(f)", "ceiling": "ceiling(f)", "floor": "floor(f)",

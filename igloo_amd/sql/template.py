@@ -20,6 +20,8 @@ reached the plan:
   operands;
 * copied into a plan field (the LIKE pattern string, ``raw``): the field is
   recomputed from the new literal;
+* a bytes literal (``X'0a0b'``) is never a slot: its text is part of the
+  template's key, so a statement with another one is planned on its own;
 * read in any other way (``Lit.value`` read during binding or optimization:
   LIMIT counts, substring positions, function options, a value that
   decides the plan's shape): the template is keyed on that literal's exact
@@ -59,6 +61,7 @@ def why(msg: str) -> None:
 _TOKEN = re.compile(r"""
     (?P<comment>--[^\n]*|/\*.*?\*/)
   | (?P<ident>"(?:[^"]|"")*"|`[^`]*`)
+  | (?P<bytes>(?<![\w$])[xX]'[^']*')
   | (?P<str>'(?:[^']|'')*')
   | (?P<num>(?<![\w$.])(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?(?![\w.]))
 """, re.X | re.S)
@@ -87,7 +90,9 @@ def lex(sql: str) -> Optional[Lexed]:
     out, spans, texts, kinds, last = [], [], [], [], 0
     for m in _TOKEN.finditer(sql):
         g = m.lastgroup
-        if g in ("comment", "ident"):
+        if g in ("comment", "ident", "bytes"):
+            # (an X'..' bytes literal is part of the statement's shape: it stays in the template's
+            # key as written, so a different one plans afresh -- keyed, not a slot)
             continue
         s, e = m.span()
         tok = m.group()

@@ -8,6 +8,11 @@ Device layout (Arrow-compatible in HBM):
   results (p > 18, e.g. SUM) may hold an [n, 2] int64 (lo, hi) int128 tensor;
 * UTF8: either plain (int64 offsets + uint8 bytes, Arrow large_string) or
   dictionary-encoded (int32 codes + a plain-string dictionary column);
+* BINARY: the plain UTF8 layout (int64 offsets + uint8 bytes, Arrow
+  large_binary) with no text semantics: ``is_string`` stays "utf8 only" and
+  ``is_varlen`` covers both for code that only moves, hashes or compares
+  bytes. Imported columns are never dictionary-encoded; ``dict_encode`` may
+  build the dictionary form for keys and ranks (its dtype stays BINARY);
 * LIST(t): an [n, 2] int64 (start, length) view per row into a child column
   of type t (so a row gather is one 16-byte gather and the child values never
   move until the result is built); STRUCT: an int64 row id per row into one
@@ -77,6 +82,15 @@ class DataType:
         return self.kind == "utf8"
 
     @property
+    def is_binary(self) -> bool:
+        return self.kind == "binary"
+
+    @property
+    def is_varlen(self) -> bool:
+        """Offsets + bytes layout (UTF8 or BINARY): what only moves, hashes or compares bytes asks."""
+        return self.kind in ("utf8", "binary")
+
+    @property
     def is_temporal(self) -> bool:
         return self.kind in ("date32", "timestamp")
 
@@ -97,6 +111,8 @@ class DataType:
             return pa.decimal128(max(self.precision, 1), self.scale)
         if k == "utf8":
             return pa.large_string()
+        if k == "binary":
+            return pa.large_binary()
         if k == "timestamp":
             return pa.timestamp("us")
         return _ARROW[k]
@@ -125,6 +141,7 @@ FLOAT64 = DataType("float64")
 DATE32 = DataType("date32")
 TIMESTAMP = DataType("timestamp")
 UTF8 = DataType("utf8")
+BINARY = DataType("binary")
 NULL = DataType("null")
 
 
@@ -132,16 +149,26 @@ def DECIMAL(p: int, s: int) -> DataType:
     return DataType("decimal", min(p, 38), s)
 
 
+def _no_nested_binary(t: DataType, inside: str) -> DataType:
+    """The nested kernels and list functions are not extended to Binary: no
+    LIST / MAP / STRUCT type is ever formed over it (Arrow import, array_agg,
+    make_array, struct, map constructors alike)."""
+    if t is not None and t.kind == "binary":
+        from .utils.errors import NotSupported
+        raise NotSupported(f"Binary inside {inside} (a Binary value must be top-level)")
+    return t
+
+
 def LIST(child: DataType) -> DataType:
-    return DataType("list", child=child)
+    return DataType("list", child=_no_nested_binary(child, "LIST"))
 
 
 def STRUCT(fields) -> DataType:
-    return DataType("struct", fields=tuple((str(n), t) for n, t in fields))
+    return DataType("struct", fields=tuple((str(n), _no_nested_binary(t, "STRUCT")) for n, t in fields))
 
 
 def MAP(key: DataType, value: DataType) -> DataType:
-    return DataType("map", fields=(("key", key), ("value", value)))
+    return DataType("map", fields=(("key", _no_nested_binary(key, "MAP")), ("value", _no_nested_binary(value, "MAP"))))
 
 
 _TORCH = {
@@ -156,6 +183,7 @@ _TORCH = {
     "timestamp": torch.int64,
     "decimal": torch.int64,
     "utf8": torch.uint8,
+    "binary": torch.uint8,
     "null": torch.bool,
     "list": torch.int64,
     "struct": torch.int64,
@@ -182,6 +210,7 @@ _NAMES = {
     "float64": "Float64",
     "date32": "Date32",
     "utf8": "Utf8",
+    "binary": "Binary",
     "null": "Null",
     "timestamp": "Timestamp(us)",
 }
@@ -217,6 +246,9 @@ def from_arrow_type(t: pa.DataType) -> DataType:
         return DECIMAL(t.precision, t.scale)
     if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_string_view(t):
         return UTF8
+    if (pa.types.is_binary(t) or pa.types.is_large_binary(t) or pa.types.is_fixed_size_binary(t)
+            or pa.types.is_binary_view(t)):
+        return BINARY
     if pa.types.is_null(t):
         return NULL
     raise PlanError(f"unsupported Arrow type {t}")
@@ -247,6 +279,8 @@ def parse_type_name(name: str) -> DataType:
         return DECIMAL(p, s)
     if base in ("VARCHAR", "CHAR", "TEXT", "STRING", "CHARACTER", "BPCHAR"):
         return UTF8
+    if base in ("BYTEA", "BINARY", "VARBINARY", "BLOB"):     # a length argument is accepted and ignored
+        return BINARY
     if base == "DATE":
         return DATE32
     if base in ("TIMESTAMP", "DATETIME"):
