@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -1072,11 +1073,10 @@ void sorted_having(const void* keys, bool key64, int64_t n, const AggDesc* descs
     return;
   }
   const dim3 g(grid_for(n, kBlock * kSortedRows, 32768)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(sorted_having_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, n, p, rep, cap, counter);
-  else
-    hipLaunchKernelGGL(sorted_having_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, n, p, rep, cap, counter);
-  check_launch("sorted_having", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("sorted_having", sorted_having_kernel<K>, g, b, 0, stream, as<K>(keys), n, p, rep, cap, counter);
+  });
 }
 
 void agg_update(const int32_t* gid, int64_t n, int ngroups, const AggDesc* descs, int nagg, hipStream_t stream,
@@ -1206,25 +1206,20 @@ void key_histogram_partitioned(const void* keys, bool key64, const uint8_t* vali
                                uint16_t* part, int32_t* counts, hipStream_t stream) {
   const int nbk = key_histogram_buckets(span);
   const size_t lds = (size_t)nbk * sizeof(int32_t);
-  if (phase == 0) {
-    if (key64)
-      hipLaunchKernelGGL(hist_count_kernel<int64_t>, dim3(kHistBlocks), dim3(kBlock), lds, stream,
-                         (const int64_t*)keys, valid, n, kmin, span, nbk, cnt);
-    else
-      hipLaunchKernelGGL(hist_count_kernel<int32_t>, dim3(kHistBlocks), dim3(kBlock), lds, stream,
-                         (const int32_t*)keys, valid, n, kmin, span, nbk, cnt);
-  } else if (phase == 1) {
-    if (key64)
-      hipLaunchKernelGGL(hist_scatter_kernel<int64_t>, dim3(kHistBlocks), dim3(kBlock), lds, stream,
-                         (const int64_t*)keys, valid, n, kmin, span, nbk, off, part);
-    else
-      hipLaunchKernelGGL(hist_scatter_kernel<int32_t>, dim3(kHistBlocks), dim3(kBlock), lds, stream,
-                         (const int32_t*)keys, valid, n, kmin, span, nbk, off, part);
-  } else {
-    hipLaunchKernelGGL(hist_bucket_kernel, dim3(nbk), dim3(kBlock), 0, stream, part, off, total, kHistBlocks, span,
-                       counts);
+  const char* what = "key_histogram_partitioned";
+  if (phase > 1) {
+    launch(what, hist_bucket_kernel, dim3(nbk), dim3(kBlock), 0, stream, part, off, total, kHistBlocks, span, counts);
+    return;
   }
-  check_launch("key_histogram_partitioned", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    if (phase == 0)
+      launch(what, hist_count_kernel<K>, dim3(kHistBlocks), dim3(kBlock), lds, stream, as<K>(keys), valid, n, kmin,
+             span, nbk, cnt);
+    else
+      launch(what, hist_scatter_kernel<K>, dim3(kHistBlocks), dim3(kBlock), lds, stream, as<K>(keys), valid, n, kmin,
+             span, nbk, off, part);
+  });
 }
 
 int key_histogram_blocks() { return kHistBlocks; }
@@ -1503,13 +1498,10 @@ void key_histogram(const void* keys, bool key64, const uint8_t* valid, int64_t n
                    int32_t* counts, hipStream_t stream) {
   if (n <= 0) return;
   const dim3 g(grid_for(n, kBlock, 1 << 16)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(key_histogram_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, valid, n, kmin, span,
-                       counts);
-  else
-    hipLaunchKernelGGL(key_histogram_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, valid, n, kmin, span,
-                       counts);
-  check_launch("key_histogram", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("key_histogram", key_histogram_kernel<K>, g, b, 0, stream, as<K>(keys), valid, n, kmin, span, counts);
+  });
 }
 }  // namespace kern
 }  // namespace igloo

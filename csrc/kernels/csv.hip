@@ -22,6 +22,7 @@
 //                     (un-escaping quoted fields) after an offset scan.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "textparse.h"
 
 namespace igloo {
@@ -298,13 +299,10 @@ void csv_rows(const uint8_t* buf, int64_t n, int64_t start, uint8_t quote, const
               int64_t* tile_rows, const int64_t* tile_off, int64_t* rows_end, hipStream_t stream) {
   const int64_t t = csv_num_tiles(n);
   if (t == 0) return;
-  if (rows_end)
-    hipLaunchKernelGGL(csv_rows_kernel<true>, dim3((unsigned)t), dim3(kWave), 0, stream, buf, n, start, quote,
-                       tile_state, tile_rows, tile_off, rows_end);
-  else
-    hipLaunchKernelGGL(csv_rows_kernel<false>, dim3((unsigned)t), dim3(kWave), 0, stream, buf, n, start, quote,
-                       tile_state, tile_rows, tile_off, rows_end);
-  check_launch("csv_rows", stream);
+  dispatch(rows_end != nullptr, [&](auto w) {
+    launch("csv_rows", csv_rows_kernel<w.value>, dim3((unsigned)t), dim3(kWave), 0, stream, buf, n, start, quote,
+           tile_state, tile_rows, tile_off, rows_end);
+  });
 }
 
 void csv_parse(const uint8_t* buf, int64_t start, const int64_t* rows_end, int64_t nrows, const CsvColumn* cols,

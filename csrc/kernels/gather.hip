@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -198,22 +199,10 @@ void gather_multi(const void* idx, bool idx64, int64_t n, const GatherDesc* desc
     p.ncols = ncols - base < kMaxGatherCols ? ncols - base : kMaxGatherCols;
     for (int c = 0; c < p.ncols; ++c) p.d[c] = descs[base + c];
     const dim3 g(grid_for(n, kBlock * kGatherRows, 65536)), b(kBlock);
-    if (idx64)
-      hipLaunchKernelGGL((gather_percol_kernel<int64_t, kGatherRows>), g, b, 0, stream, (const int64_t*)idx, n, p);
-    else
-      hipLaunchKernelGGL((gather_percol_kernel<int32_t, kGatherRows>), g, b, 0, stream, (const int32_t*)idx, n, p);
-    check_launch("gather_multi", stream);
-  }
-}
-
-template <typename I>
-static void launch_packed(const I* idx, int64_t n, const PackedParams& p, int words, hipStream_t stream) {
-  const dim3 g(grid_for(n, kBlock * kGatherRows, 65536)), b(kBlock);
-  switch (words) {
-    case 1: hipLaunchKernelGGL((gather_packed_kernel<I, 1>), g, b, 0, stream, idx, n, p); break;
-    case 2: hipLaunchKernelGGL((gather_packed_kernel<I, 2>), g, b, 0, stream, idx, n, p); break;
-    case 3: hipLaunchKernelGGL((gather_packed_kernel<I, 3>), g, b, 0, stream, idx, n, p); break;
-    default: hipLaunchKernelGGL((gather_packed_kernel<I, 4>), g, b, 0, stream, idx, n, p); break;
+    dispatch(wide{idx64}, [&](auto i) {
+      using I = type_of<decltype(i)>;
+      launch("gather_multi", gather_percol_kernel<I, kGatherRows>, g, b, 0, stream, as<I>(idx), n, p);
+    });
   }
 }
 
@@ -237,35 +226,35 @@ void gather_packed(const void* idx, bool idx64, int64_t n, const uint8_t* src, i
       throw std::runtime_error("gather_packed: bad field " + std::to_string(f));
     p.f[f] = d;
   }
-  if (idx64)
-    launch_packed(static_cast<const int64_t*>(idx), n, p, row_bytes / 8, stream);
-  else
-    launch_packed(static_cast<const int32_t*>(idx), n, p, row_bytes / 8, stream);
-  check_launch("gather_packed", stream);
+  const dim3 g(grid_for(n, kBlock * kGatherRows, 65536)), b(kBlock);
+  dispatch(wide{idx64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    // one kernel per row width in 8-byte words (1..4, checked above)
+    void (*const by_words[])(const I*, int64_t, PackedParams) = {
+        gather_packed_kernel<I, 1>, gather_packed_kernel<I, 2>, gather_packed_kernel<I, 3>, gather_packed_kernel<I, 4>};
+    launch("gather_packed", by_words[row_bytes / 8 - 1], g, b, 0, stream, as<I>(idx), n, p);
+  });
 }
 
 void str_gather_lengths(const int64_t* off, int64_t src_rows, const void* idx, bool idx64, int64_t n, int64_t* len,
                         hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, 65536)), b(kBlock);
-  if (idx64)
-    hipLaunchKernelGGL(str_lengths_kernel<int64_t>, g, b, 0, stream, off, src_rows, (const int64_t*)idx, n, len);
-  else
-    hipLaunchKernelGGL(str_lengths_kernel<int32_t>, g, b, 0, stream, off, src_rows, (const int32_t*)idx, n, len);
-  check_launch("str_gather_lengths", stream);
+  dispatch(wide{idx64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    launch("str_gather_lengths", str_lengths_kernel<I>, g, b, 0, stream, off, src_rows, as<I>(idx), n, len);
+  });
 }
 
 void str_gather_copy(const int64_t* off, int64_t src_rows, const uint8_t* chars, const void* idx, bool idx64,
                      int64_t n, const int64_t* new_off, uint8_t* out, int64_t out_cap, hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock / 8, 65536)), b(kBlock);
-  if (idx64)
-    hipLaunchKernelGGL(str_copy_kernel<int64_t>, g, b, 0, stream, off, src_rows, chars, (const int64_t*)idx, n, new_off,
-                       out, out_cap);
-  else
-    hipLaunchKernelGGL(str_copy_kernel<int32_t>, g, b, 0, stream, off, src_rows, chars, (const int32_t*)idx, n, new_off,
-                       out, out_cap);
-  check_launch("str_gather_copy", stream);
+  dispatch(wide{idx64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    launch("str_gather_copy", str_copy_kernel<I>, g, b, 0, stream, off, src_rows, chars, as<I>(idx), n, new_off, out,
+           out_cap);
+  });
 }
 
 }  // namespace kern

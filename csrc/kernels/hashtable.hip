@@ -20,6 +20,7 @@
 // probe outputs) are int32 below 2^31 build rows and int64 above (R).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 #include <cmath>
 #include <cstdint>
@@ -438,48 +439,35 @@ __global__ __launch_bounds__(kBlock) void fill_runs_kernel(const I* __restrict__
 void fill_runs(const void* starts, bool starts64, int64_t nruns, int64_t n, int32_t* gid, hipStream_t stream) {
   if (nruns == 0) return;
   dim3 g(grid_for(nruns, kBlock, kMaxGrid)), b(kBlock);
-  if (starts64) hipLaunchKernelGGL(fill_runs_kernel<int64_t>, g, b, 0, stream, (const int64_t*)starts, nruns, n, gid);
-  else hipLaunchKernelGGL(fill_runs_kernel<int32_t>, g, b, 0, stream, (const int32_t*)starts, nruns, n, gid);
-  check_launch("fill_runs", stream);
+  dispatch(wide{starts64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    launch("fill_runs", fill_runs_kernel<I>, g, b, 0, stream, as<I>(starts), nruns, n, gid);
+  });
 }
-
-// launch KERNEL<K, DIRECT, R> with keys cast to the key type
-#define DISPATCH_KEY3(key64, direct, R, KERNEL, g, b, shm, st, keys, ...)                                  \
-  do {                                                                                                    \
-    if (key64) {                                                                                          \
-      if (direct) hipLaunchKernelGGL((KERNEL<int64_t, true, R>), g, b, shm, st, (const int64_t*)(keys), __VA_ARGS__); \
-      else hipLaunchKernelGGL((KERNEL<int64_t, false, R>), g, b, shm, st, (const int64_t*)(keys), __VA_ARGS__);       \
-    } else {                                                                                              \
-      if (direct) hipLaunchKernelGGL((KERNEL<int32_t, true, R>), g, b, shm, st, (const int32_t*)(keys), __VA_ARGS__); \
-      else hipLaunchKernelGGL((KERNEL<int32_t, false, R>), g, b, shm, st, (const int32_t*)(keys), __VA_ARGS__);       \
-    }                                                                                                     \
-  } while (0)
 
 void join_build(const void* keys, bool key64, const uint8_t* valid, int64_t n, int64_t* tkeys, void* thead, bool rid64,
                 int64_t cap, int64_t kmin, bool direct, unsigned long long* dups, uint32_t* bits, uint64_t bmask,
                 hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, kMaxGrid)), b(kBlock);
-  if (rid64)
-    DISPATCH_KEY3(key64, direct, int64_t, join_build_kernel, g, b, 0, stream, keys, valid, n, tkeys, (int64_t*)thead,
-                  cap, kmin, dups, bits, bmask);
-  else
-    DISPATCH_KEY3(key64, direct, int32_t, join_build_kernel, g, b, 0, stream, keys, valid, n, tkeys, (int32_t*)thead,
-                  cap, kmin, dups, bits, bmask);
-  check_launch("join_build", stream);
+  dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    launch("join_build", join_build_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, n, tkeys,
+           as<R>(thead), cap, kmin, dups, bits, bmask);
+  });
 }
 
 void join_csr_count(const void* keys, bool key64, const uint8_t* valid, int64_t n, const int64_t* tkeys, void* cnt,
                     bool rid64, int64_t cap, int64_t kmin, bool direct, hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, kMaxGrid)), b(kBlock);
-  if (rid64)
-    DISPATCH_KEY3(key64, direct, int64_t, join_csr_count_kernel, g, b, 0, stream, keys, valid, n, tkeys, (int64_t*)cnt,
-                  cap, kmin);
-  else
-    DISPATCH_KEY3(key64, direct, int32_t, join_csr_count_kernel, g, b, 0, stream, keys, valid, n, tkeys, (int32_t*)cnt,
-                  cap, kmin);
-  check_launch("join_csr_count", stream);
+  dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    launch("join_csr_count", join_csr_count_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, n, tkeys,
+           as<R>(cnt), cap, kmin);
+  });
 }
 
 void join_csr_scatter(const void* keys, bool key64, const uint8_t* valid, int64_t n, const int64_t* tkeys, void* cnt,
@@ -487,36 +475,12 @@ void join_csr_scatter(const void* keys, bool key64, const uint8_t* valid, int64_
                       hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, kMaxGrid)), b(kBlock);
-  if (rid64)
-    DISPATCH_KEY3(key64, direct, int64_t, join_csr_scatter_kernel, g, b, 0, stream, keys, valid, n, tkeys,
-                  (int64_t*)cnt, (const int64_t*)cstart, (int64_t*)crows, cap, kmin);
-  else
-    DISPATCH_KEY3(key64, direct, int32_t, join_csr_scatter_kernel, g, b, 0, stream, keys, valid, n, tkeys,
-                  (int32_t*)cnt, (const int32_t*)cstart, (int32_t*)crows, cap, kmin);
-  check_launch("join_csr_scatter", stream);
-}
-
-template <typename R>
-static void join_probe_t(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                         const R* thead, const R* cstart, const R* crows, int64_t cap, int64_t kmin, bool direct,
-                         int32_t* counts, R* first, uint8_t* build_matched, const uint32_t* bits, uint64_t bmask,
-                         hipStream_t stream) {
-  const dim3 b(kBlock);
-  if (direct && first && !counts && !build_matched && !cstart) {
-    const dim3 g4(grid_for((m + kProbeRows - 1) / kProbeRows, kBlock, kMaxGrid));
-    if (key64)
-      hipLaunchKernelGGL((join_probe_first_direct_kernel<int64_t, R>), g4, b, 0, stream, (const int64_t*)keys, valid,
-                         m, thead, cap, kmin, first, bits, bmask);
-    else
-      hipLaunchKernelGGL((join_probe_first_direct_kernel<int32_t, R>), g4, b, 0, stream, (const int32_t*)keys, valid,
-                         m, thead, cap, kmin, first, bits, bmask);
-    check_launch("join_probe_first_direct", stream);
-    return;
-  }
-  const dim3 g(grid_for(m, kBlock, kMaxGrid));
-  DISPATCH_KEY3(key64, direct, R, join_probe_kernel, g, b, 0, stream, keys, valid, m, tkeys, thead, cstart, crows, cap,
-                kmin, counts, first, build_matched, bits, bmask);
-  check_launch("join_probe", stream);
+  dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    launch("join_csr_scatter", join_csr_scatter_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, n, tkeys,
+           as<R>(cnt), as<R>(cstart), as<R>(crows), cap, kmin);
+  });
 }
 
 void join_probe(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
@@ -524,14 +488,23 @@ void join_probe(const void* keys, bool key64, const uint8_t* valid, int64_t m, c
                 bool direct, int32_t* counts, void* first, uint8_t* build_matched, const uint32_t* bits,
                 uint64_t bmask, hipStream_t stream) {
   if (m == 0) return;
-  if (rid64)
-    join_probe_t<int64_t>(keys, key64, valid, m, tkeys, (const int64_t*)thead, (const int64_t*)cstart,
-                          (const int64_t*)crows, cap, kmin, direct, counts, (int64_t*)first, build_matched, bits,
-                          bmask, stream);
-  else
-    join_probe_t<int32_t>(keys, key64, valid, m, tkeys, (const int32_t*)thead, (const int32_t*)cstart,
-                          (const int32_t*)crows, cap, kmin, direct, counts, (int32_t*)first, build_matched, bits,
-                          bmask, stream);
+  const dim3 b(kBlock);
+  const bool first_direct = direct && first && !counts && !build_matched && !cstart;
+  dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    if constexpr (d.value) {
+      if (first_direct) {
+        const dim3 g4(grid_for((m + kProbeRows - 1) / kProbeRows, kBlock, kMaxGrid));
+        launch("join_probe_first_direct", join_probe_first_direct_kernel<K, R>, g4, b, 0, stream, as<K>(keys), valid,
+               m, as<R>(thead), cap, kmin, as<R>(first), bits, bmask);
+        return;
+      }
+    }
+    const dim3 g(grid_for(m, kBlock, kMaxGrid));
+    launch("join_probe", join_probe_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, m, tkeys,
+           as<R>(thead), as<R>(cstart), as<R>(crows), cap, kmin, counts, as<R>(first), build_matched, bits, bmask);
+  });
 }
 
 void join_expand(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
@@ -540,72 +513,58 @@ void join_expand(const void* keys, bool key64, const uint8_t* valid, int64_t m, 
                  uint64_t bmask, int64_t out_cap, hipStream_t stream) {
   if (m == 0) return;
   dim3 g(grid_for(m, kBlock, kMaxGrid)), b(kBlock);
-  if (rid64)
-    DISPATCH_KEY3(key64, direct, int64_t, join_expand_kernel, g, b, 0, stream, keys, valid, m, tkeys,
-                  (const int64_t*)thead, (const int64_t*)cstart, (const int64_t*)crows, cap, kmin, offsets, out_probe,
-                  (int64_t*)out_build, bits, bmask, out_cap);
-  else
-    DISPATCH_KEY3(key64, direct, int32_t, join_expand_kernel, g, b, 0, stream, keys, valid, m, tkeys,
-                  (const int32_t*)thead, (const int32_t*)cstart, (const int32_t*)crows, cap, kmin, offsets, out_probe,
-                  (int32_t*)out_build, bits, bmask, out_cap);
-  check_launch("join_expand", stream);
+  dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    launch("join_expand", join_expand_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, m, tkeys,
+           as<R>(thead), as<R>(cstart), as<R>(crows), cap, kmin, offsets, out_probe, as<R>(out_build), bits, bmask,
+           out_cap);
+  });
 }
 
 void groupby_build(const void* keys, bool key64, int64_t n, int64_t* tkeys, int32_t* trow, int64_t cap, int64_t kmin,
                    bool direct, hipStream_t stream) {
   if (n == 0) return;
-  if (direct && cap <= kGroupLdsSlots) {
-    // a few hundred workgroups: enough to fill the CUs, few end-of-block merges
-    const dim3 g(grid_for(n, kBlock * 16, 1024)), b(kBlock);
-    if (key64)
-      hipLaunchKernelGGL(groupby_build_lds_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, n, trow, cap, kmin);
-    else
-      hipLaunchKernelGGL(groupby_build_lds_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, n, trow, cap, kmin);
-    check_launch("groupby_build_lds", stream);
-    return;
-  }
-  // (hashed: several rows per lane, so each workgroup's row cache covers many rows)
-  dim3 g(grid_for(n, direct ? kBlock : kBlock * 8, kMaxGrid)), b(kBlock);
-  if (key64) {
-    if (direct) hipLaunchKernelGGL((groupby_build_kernel<int64_t, true>), g, b, 0, stream, (const int64_t*)keys, n, tkeys, trow, cap, kmin);
-    else hipLaunchKernelGGL((groupby_build_kernel<int64_t, false>), g, b, 0, stream, (const int64_t*)keys, n, tkeys, trow, cap, kmin);
-  } else {
-    if (direct) hipLaunchKernelGGL((groupby_build_kernel<int32_t, true>), g, b, 0, stream, (const int32_t*)keys, n, tkeys, trow, cap, kmin);
-    else hipLaunchKernelGGL((groupby_build_kernel<int32_t, false>), g, b, 0, stream, (const int32_t*)keys, n, tkeys, trow, cap, kmin);
-  }
-  check_launch("groupby_build", stream);
+  const bool lds = direct && cap <= kGroupLdsSlots;
+  dispatch(wide{key64}, direct, [&](auto k, auto d) {
+    using K = type_of<decltype(k)>;
+    const dim3 b(kBlock);
+    if (lds) {
+      // a few hundred workgroups: enough to fill the CUs, few end-of-block merges
+      const dim3 g(grid_for(n, kBlock * 16, 1024));
+      launch("groupby_build_lds", groupby_build_lds_kernel<K>, g, b, 0, stream, as<K>(keys), n, trow, cap, kmin);
+      return;
+    }
+    // (hashed: several rows per lane, so each workgroup's row cache covers many rows)
+    const dim3 g(grid_for(n, direct ? kBlock : kBlock * 8, kMaxGrid));
+    launch("groupby_build", groupby_build_kernel<K, d.value>, g, b, 0, stream, as<K>(keys), n, tkeys, trow, cap, kmin);
+  });
 }
 
 void groupby_occupied(const int32_t* trow, int64_t cap, uint8_t* occ, int32_t* gid_of_slot, hipStream_t stream) {
-  hipLaunchKernelGGL(occupied_kernel, dim3(grid_for(cap, kBlock, kMaxGrid)), dim3(kBlock), 0, stream, trow, cap, occ, gid_of_slot);
-  check_launch("groupby_occupied", stream);
+  launch("groupby_occupied", occupied_kernel, dim3(grid_for(cap, kBlock, kMaxGrid)), dim3(kBlock), 0, stream, trow, cap,
+         occ, gid_of_slot);
 }
 
 void groupby_assign(const void* slots, bool slots64, int64_t g, int64_t cap, const int32_t* trow,
                     int32_t* gid_of_slot, int32_t* rep_row, hipStream_t stream) {
   if (g == 0) return;
   dim3 gr(grid_for(g, kBlock, kMaxGrid)), b(kBlock);
-  if (slots64)
-    hipLaunchKernelGGL(assign_gid_kernel<int64_t>, gr, b, 0, stream, (const int64_t*)slots, g, cap, trow, gid_of_slot,
-                       rep_row);
-  else
-    hipLaunchKernelGGL(assign_gid_kernel<int32_t>, gr, b, 0, stream, (const int32_t*)slots, g, cap, trow, gid_of_slot,
-                       rep_row);
-  check_launch("groupby_assign", stream);
+  dispatch(wide{slots64}, [&](auto s) {
+    using S = type_of<decltype(s)>;
+    launch("groupby_assign", assign_gid_kernel<S>, gr, b, 0, stream, as<S>(slots), g, cap, trow, gid_of_slot, rep_row);
+  });
 }
 
 void groupby_lookup(const void* keys, bool key64, int64_t n, const int64_t* tkeys, const int32_t* gid_of_slot,
                     int64_t cap, int64_t kmin, bool direct, int32_t* gid, hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, kMaxGrid)), b(kBlock);
-  if (key64) {
-    if (direct) hipLaunchKernelGGL((groupby_lookup_kernel<int64_t, true>), g, b, 0, stream, (const int64_t*)keys, n, tkeys, gid_of_slot, cap, kmin, gid);
-    else hipLaunchKernelGGL((groupby_lookup_kernel<int64_t, false>), g, b, 0, stream, (const int64_t*)keys, n, tkeys, gid_of_slot, cap, kmin, gid);
-  } else {
-    if (direct) hipLaunchKernelGGL((groupby_lookup_kernel<int32_t, true>), g, b, 0, stream, (const int32_t*)keys, n, tkeys, gid_of_slot, cap, kmin, gid);
-    else hipLaunchKernelGGL((groupby_lookup_kernel<int32_t, false>), g, b, 0, stream, (const int32_t*)keys, n, tkeys, gid_of_slot, cap, kmin, gid);
-  }
-  check_launch("groupby_lookup", stream);
+  dispatch(wide{key64}, direct, [&](auto k, auto d) {
+    using K = type_of<decltype(k)>;
+    launch("groupby_lookup", groupby_lookup_kernel<K, d.value>, g, b, 0, stream, as<K>(keys), n, tkeys, gid_of_slot,
+           cap, kmin, gid);
+  });
 }
 
 }  // namespace kern
@@ -1298,28 +1257,6 @@ void probe_fold_build(const uint32_t* bits, int64_t cap, uint32_t* fold, hipStre
   check_launch("probe_fold_build", stream);
 }
 
-template <typename K, bool NARROW>
-static void launch_fold(ProbeKernel plan, const void* keys, const uint8_t* valid, int64_t m, int64_t cap, int64_t kmin,
-                        const uint32_t* bits, const uint32_t* fold, bool negate, unsigned long long* words,
-                        int64_t* tile_counts, hipStream_t stream) {
-  const int64_t tiles = probe_hit_tiles(m);
-  const K* k = static_cast<const K*>(keys);
-  const dim3 bf(kFoldBlock);
-  if (plan == kProbeFold) {
-    const dim3 gf(grid_for(tiles, 1, kFoldGrid));
-    hipLaunchKernelGGL((probe_fold_kernel<K, NARROW>), gf, bf, 0, stream, k, valid, m, cap, kmin, bits, fold, negate,
-                       words, tile_counts);
-    return;
-  }
-  const dim3 gs(grid_for(tiles, kFoldWaves, kFoldGrid));
-  if (valid)
-    hipLaunchKernelGGL((probe_stream_kernel<K, NARROW, true>), gs, bf, 0, stream, k, valid, m, cap, kmin, bits, fold,
-                       negate, words, tile_counts);
-  else
-    hipLaunchKernelGGL((probe_stream_kernel<K, NARROW, false>), gs, bf, 0, stream, k, valid, m, cap, kmin, bits, fold,
-                       negate, words, tile_counts);
-}
-
 void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
                 const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const uint32_t* bits,
                 uint64_t bmask, bool negate, int64_t n_build, const uint32_t* fold, unsigned long long* words,
@@ -1331,30 +1268,38 @@ void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, c
   ProbeKernel plan = probe_plan(vec, m, cap, n_build);
   // (the fold kernels copy the bitmap, or its fold, with 16-byte loads)
   if (plan >= kProbeFold && (((uintptr_t)bits | (uintptr_t)fold) & 15)) plan = kProbeBits;
+  g_last_probe = plan;
   if (plan >= kProbeFold) {
     if (((cap + 31) >> 5) > kFoldWords && !fold)
       throw std::runtime_error("probe_hits: a bitmap wider than the fold needs probe_fold_build's scratch");
-    if (key64)
-      launch_fold<int64_t, false>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
-    else if (kmin >= INT32_MIN && cap < (1LL << 31) && kmin + cap <= (1LL << 31))
-      launch_fold<int32_t, true>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
-    else
-      launch_fold<int32_t, false>(plan, keys, valid, m, cap, kmin, bits, fold, negate, words, tile_counts, stream);
+    const bool narrow = !key64 && kmin >= INT32_MIN && cap < (1LL << 31) && kmin + cap <= (1LL << 31);
+    const int64_t tiles = probe_hit_tiles(m);
+    const dim3 bf(kFoldBlock);
+    dispatch(wide{key64}, narrow, valid != nullptr, [&](auto k, auto nr, auto v) {
+      using K = type_of<decltype(k)>;
+      if constexpr (sizeof(K) == 4 || !nr.value) {  // NARROW exists for int32 keys only
+        if (plan == kProbeFold)
+          launch("probe_hits", probe_fold_kernel<K, nr.value>, dim3(grid_for(tiles, 1, kFoldGrid)), bf, 0, stream,
+                 as<K>(keys), valid, m, cap, kmin, bits, fold, negate, words, tile_counts);
+        else
+          launch("probe_hits", probe_stream_kernel<K, nr.value, v.value>, dim3(grid_for(tiles, kFoldWaves, kFoldGrid)),
+                 bf, 0, stream, as<K>(keys), valid, m, cap, kmin, bits, fold, negate, words, tile_counts);
+      }
+    });
   } else if (plan == kProbeBits) {
-    if (key64)
-      hipLaunchKernelGGL(probe_bits_kernel<int64_t>, g, b, 0, stream, static_cast<const int64_t*>(keys), valid, m, cap,
-                         kmin, bits, negate, words, tile_counts);
-    else
-      hipLaunchKernelGGL(probe_bits_kernel<int32_t>, g, b, 0, stream, static_cast<const int32_t*>(keys), valid, m, cap,
-                         kmin, bits, negate, words, tile_counts);
-  } else if (rid64)
-    DISPATCH_KEY3(key64, direct, int64_t, probe_hits_kernel, g, b, 0, stream, keys, valid, m, tkeys,
-                  (const int64_t*)thead, cap, kmin, bits, bmask, negate, words, tile_counts);
-  else
-    DISPATCH_KEY3(key64, direct, int32_t, probe_hits_kernel, g, b, 0, stream, keys, valid, m, tkeys,
-                  (const int32_t*)thead, cap, kmin, bits, bmask, negate, words, tile_counts);
-  g_last_probe = plan;
-  check_launch("probe_hits", stream);
+    dispatch(wide{key64}, [&](auto k) {
+      using K = type_of<decltype(k)>;
+      launch("probe_hits", probe_bits_kernel<K>, g, b, 0, stream, as<K>(keys), valid, m, cap, kmin, bits, negate, words,
+             tile_counts);
+    });
+  } else {
+    dispatch(wide{key64}, direct, wide{rid64}, [&](auto k, auto d, auto r) {
+      using K = type_of<decltype(k)>;
+      using R = type_of<decltype(r)>;
+      launch("probe_hits", probe_hits_kernel<K, d.value, R>, g, b, 0, stream, as<K>(keys), valid, m, tkeys,
+             as<R>(thead), cap, kmin, bits, bmask, negate, words, tile_counts);
+    });
+  }
 }
 
 void join_table_init(void* thead, bool rid64, int64_t cap, int64_t* tkeys, uint32_t* bits, int64_t nbw,
@@ -1371,49 +1316,19 @@ void join_table_init(void* thead, bool rid64, int64_t cap, int64_t* tkeys, uint3
   check_launch("join_table_init", stream);
 }
 
-template <typename R, typename O>
-static void probe_write_t(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                          const R* thead, int64_t cap, int64_t kmin, bool direct, const unsigned long long* words,
-                          const int64_t* tile_off, O* out_probe, R* out_build, int64_t out_cap, hipStream_t stream) {
-  const dim3 g(grid_for(probe_hit_tiles(m), 1, g_probe_grid_cap)), b(kBlock);
-  if (key64) {
-    if (direct)
-      hipLaunchKernelGGL((probe_write_kernel<int64_t, true, R, O>), g, b, 0, stream, (const int64_t*)keys, valid, m,
-                         tkeys, thead, cap, kmin, words, tile_off, out_probe, out_build, out_cap);
-    else
-      hipLaunchKernelGGL((probe_write_kernel<int64_t, false, R, O>), g, b, 0, stream, (const int64_t*)keys, valid, m,
-                         tkeys, thead, cap, kmin, words, tile_off, out_probe, out_build, out_cap);
-  } else {
-    if (direct)
-      hipLaunchKernelGGL((probe_write_kernel<int32_t, true, R, O>), g, b, 0, stream, (const int32_t*)keys, valid, m,
-                         tkeys, thead, cap, kmin, words, tile_off, out_probe, out_build, out_cap);
-    else
-      hipLaunchKernelGGL((probe_write_kernel<int32_t, false, R, O>), g, b, 0, stream, (const int32_t*)keys, valid, m,
-                         tkeys, thead, cap, kmin, words, tile_off, out_probe, out_build, out_cap);
-  }
-  check_launch("probe_write", stream);
-}
-
 void probe_write(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
                  const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const unsigned long long* words,
                  const int64_t* tile_off, void* out_probe, bool out64, void* out_build, int64_t out_cap,
                  hipStream_t stream) {
   if (m == 0) return;
-  if (rid64) {
-    if (out64)
-      probe_write_t<int64_t, int64_t>(keys, key64, valid, m, tkeys, (const int64_t*)thead, cap, kmin, direct, words,
-                                      tile_off, (int64_t*)out_probe, (int64_t*)out_build, out_cap, stream);
-    else
-      probe_write_t<int64_t, int32_t>(keys, key64, valid, m, tkeys, (const int64_t*)thead, cap, kmin, direct, words,
-                                      tile_off, (int32_t*)out_probe, (int64_t*)out_build, out_cap, stream);
-  } else {
-    if (out64)
-      probe_write_t<int32_t, int64_t>(keys, key64, valid, m, tkeys, (const int32_t*)thead, cap, kmin, direct, words,
-                                      tile_off, (int64_t*)out_probe, (int32_t*)out_build, out_cap, stream);
-    else
-      probe_write_t<int32_t, int32_t>(keys, key64, valid, m, tkeys, (const int32_t*)thead, cap, kmin, direct, words,
-                                      tile_off, (int32_t*)out_probe, (int32_t*)out_build, out_cap, stream);
-  }
+  const dim3 g(grid_for(probe_hit_tiles(m), 1, g_probe_grid_cap)), b(kBlock);
+  dispatch(wide{key64}, direct, wide{rid64}, wide{out64}, [&](auto k, auto d, auto r, auto o) {
+    using K = type_of<decltype(k)>;
+    using R = type_of<decltype(r)>;
+    using O = type_of<decltype(o)>;
+    launch("probe_write", probe_write_kernel<K, d.value, R, O>, g, b, 0, stream, as<K>(keys), valid, m, tkeys,
+           as<R>(thead), cap, kmin, words, tile_off, as<O>(out_probe), as<R>(out_build), out_cap);
+  });
 }
 }  // namespace kern
 }  // namespace igloo

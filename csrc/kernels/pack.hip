@@ -12,6 +12,7 @@
 // 64 consecutive rows (one contiguous 64 x row_bytes span) per column.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -63,18 +64,16 @@ __global__ __launch_bounds__(kBlock) void unpack_rows_kernel(PackSpec spec, cons
 void pack_rows(const PackSpec& spec, const void* perm, bool perm64, int64_t n, uint8_t* out, hipStream_t stream) {
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock, 8192);
-  if (perm64)
-    hipLaunchKernelGGL(pack_rows_kernel<int64_t>, dim3(g), dim3(kBlock), 0, stream, spec, (const int64_t*)perm, n, out);
-  else
-    hipLaunchKernelGGL(pack_rows_kernel<int32_t>, dim3(g), dim3(kBlock), 0, stream, spec, (const int32_t*)perm, n, out);
-  check_launch("pack.rows", stream);
+  dispatch(wide{perm64}, [&](auto p) {
+    using P = type_of<decltype(p)>;
+    launch("pack.rows", pack_rows_kernel<P>, dim3(g), dim3(kBlock), 0, stream, spec, as<P>(perm), n, out);
+  });
 }
 
 void unpack_rows(const PackSpec& spec, const uint8_t* in, int64_t n, hipStream_t stream) {
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock, 8192);
-  hipLaunchKernelGGL(unpack_rows_kernel, dim3(g), dim3(kBlock), 0, stream, spec, in, n);
-  check_launch("pack.unpack", stream);
+  launch("pack.unpack", unpack_rows_kernel, dim3(g), dim3(kBlock), 0, stream, spec, in, n);
 }
 
 }  // namespace kern

@@ -11,6 +11,7 @@
 //      row's rank inside its wave; LDS carries the per-part running offset).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -134,11 +135,11 @@ void partition_hist(const void* keys, bool key64, int64_t n, int nparts, int64_t
   if (nparts > kMaxParts) throw std::runtime_error("partition_hist: too many partitions");
   int64_t blocks = partition_blocks(n);
   int64_t rpb = (n + blocks - 1) / blocks;
-  if (key64)
-    hipLaunchKernelGGL(part_hist_kernel<int64_t>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (const int64_t*)keys, n, nparts, rpb, counts);
-  else
-    hipLaunchKernelGGL(part_hist_kernel<int32_t>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (const int32_t*)keys, n, nparts, rpb, counts);
-  check_launch("partition_hist", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("partition_hist", part_hist_kernel<K>, dim3((unsigned)blocks), dim3(kBlock), 0, stream, as<K>(keys), n,
+           nparts, rpb, counts);
+  });
 }
 
 void partition_run(const void* keys, bool key64, int64_t n, int nparts, int64_t* counts_ws, int64_t* total,
@@ -149,20 +150,14 @@ void partition_run(const void* keys, bool key64, int64_t n, int nparts, int64_t*
   rpb = (rpb + kBlock - 1) / kBlock * kBlock;
   blocks = n > 0 ? (n + rpb - 1) / rpb : 1;
   dim3 g((unsigned)blocks), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(part_hist_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, n, nparts, rpb, counts_ws);
-  else
-    hipLaunchKernelGGL(part_hist_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, n, nparts, rpb, counts_ws);
-  check_launch("partition_hist", stream);
-  scan_counts(counts_ws, (int64_t)nparts * blocks, total, stream);
-  if (key64) {
-    if (perm64) hipLaunchKernelGGL((part_scatter_kernel<int64_t, int64_t>), g, b, 0, stream, (const int64_t*)keys, n, nparts, rpb, counts_ws, (int64_t*)perm);
-    else hipLaunchKernelGGL((part_scatter_kernel<int64_t, int32_t>), g, b, 0, stream, (const int64_t*)keys, n, nparts, rpb, counts_ws, (int32_t*)perm);
-  } else {
-    if (perm64) hipLaunchKernelGGL((part_scatter_kernel<int32_t, int64_t>), g, b, 0, stream, (const int32_t*)keys, n, nparts, rpb, counts_ws, (int64_t*)perm);
-    else hipLaunchKernelGGL((part_scatter_kernel<int32_t, int32_t>), g, b, 0, stream, (const int32_t*)keys, n, nparts, rpb, counts_ws, (int32_t*)perm);
-  }
-  check_launch("partition_scatter", stream);
+  dispatch(wide{key64}, wide{perm64}, [&](auto k, auto i) {
+    using K = type_of<decltype(k)>;
+    using I = type_of<decltype(i)>;
+    launch("partition_hist", part_hist_kernel<K>, g, b, 0, stream, as<K>(keys), n, nparts, rpb, counts_ws);
+    scan_counts(counts_ws, (int64_t)nparts * blocks, total, stream);
+    launch("partition_scatter", part_scatter_kernel<K, I>, g, b, 0, stream, as<K>(keys), n, nparts, rpb, counts_ws,
+           as<I>(perm));
+  });
 }
 
 int64_t partition_run_blocks(int64_t n) {
@@ -175,17 +170,15 @@ int64_t partition_run_blocks(int64_t n) {
 void partition_ids(const void* keys, bool key64, int64_t n, int nparts, int32_t* out, hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, 65536)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(part_ids_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, n, nparts, out);
-  else
-    hipLaunchKernelGGL(part_ids_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, n, nparts, out);
-  check_launch("partition_ids", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("partition_ids", part_ids_kernel<K>, g, b, 0, stream, as<K>(keys), n, nparts, out);
+  });
 }
 
 void date_part(const int32_t* days, int64_t n, int field, int32_t* out, hipStream_t stream) {
   if (n == 0) return;
-  hipLaunchKernelGGL(date_part_kernel, dim3(grid_for(n, kBlock, 65536)), dim3(kBlock), 0, stream, days, n, field, out);
-  check_launch("date_part", stream);
+  launch("date_part", date_part_kernel, dim3(grid_for(n, kBlock, 65536)), dim3(kBlock), 0, stream, days, n, field, out);
 }
 
 }  // namespace kern

@@ -15,6 +15,7 @@
 //     row writing its run: 17 ms for one 60M-pair expansion at SF100).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -166,28 +167,22 @@ void sorted_ranges(const void* big, bool key64, int64_t nb, const void* q, const
                    int64_t* lo, int64_t* cnt, const void* fence, int64_t nf, hipStream_t stream) {
   if (nq <= 0) return;
   const unsigned grid = grid_for(nq, kBlock, 1 << 16);
-  if (key64)
-    hipLaunchKernelGGL(sorted_ranges_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, stream,
-                       static_cast<const int64_t*>(big), nb, static_cast<const int64_t*>(q), qvalid, nq, lo, cnt,
-                       static_cast<const int64_t*>(fence), nf);
-  else
-    hipLaunchKernelGGL(sorted_ranges_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, stream,
-                       static_cast<const int32_t*>(big), nb, static_cast<const int32_t*>(q), qvalid, nq, lo, cnt,
-                       static_cast<const int32_t*>(fence), nf);
-  check_launch("sorted_ranges", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("sorted_ranges", sorted_ranges_kernel<K>, dim3(grid), dim3(kBlock), 0, stream, as<K>(big), nb, as<K>(q),
+           qvalid, nq, lo, cnt, as<K>(fence), nf);
+  });
 }
 
 void expand_ranges(const int64_t* off, const int64_t* lo, int64_t ns, int64_t total, void* sidx, void* bidx,
                    bool out64, hipStream_t stream) {
   if (total <= 0 || ns <= 0) return;
   const unsigned grid = (unsigned)((total + kExpTile - 1) / kExpTile);
-  if (out64)
-    hipLaunchKernelGGL(expand_ranges_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, stream, off, lo, ns, total,
-                       static_cast<int64_t*>(sidx), static_cast<int64_t*>(bidx));
-  else
-    hipLaunchKernelGGL(expand_ranges_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, stream, off, lo, ns, total,
-                       static_cast<int32_t*>(sidx), static_cast<int32_t*>(bidx));
-  check_launch("expand_ranges", stream);
+  dispatch(wide{out64}, [&](auto o) {
+    using O = type_of<decltype(o)>;
+    launch("expand_ranges", expand_ranges_kernel<O>, dim3(grid), dim3(kBlock), 0, stream, off, lo, ns, total,
+           as<O>(sidx), as<O>(bidx));
+  });
 }
 
 }  // namespace kern
@@ -246,22 +241,22 @@ __global__ __launch_bounds__(kBlock) void sorted_match_kernel(const K2* __restri
   }
 }
 
+// the count pass (no offsets yet) exists with 32-bit outputs only
 template <typename K2, bool MASKED>
-void launch_match(const void* big2, const void* small2, const int64_t* lo, const int64_t* cnt, int64_t ns,
-                  int32_t* counts, const int64_t* offsets, void* sidx, void* bidx, bool out64, int64_t out_cap,
-                  int32_t* first, hipStream_t stream) {
+void launch_match(const char* what, const void* big2, const void* small2, const int64_t* lo, const int64_t* cnt,
+                  int64_t ns, int32_t* counts, const int64_t* offsets, void* sidx, void* bidx, bool out64,
+                  int64_t out_cap, int32_t* first, hipStream_t stream) {
   const dim3 g(grid_for(ns, kBlock, 1 << 16)), b(kBlock);
-  const K2* B = static_cast<const K2*>(big2);
-  const K2* S = static_cast<const K2*>(small2);
-  if (!offsets)
-    hipLaunchKernelGGL((sorted_match_kernel<K2, int32_t, false, MASKED>), g, b, 0, stream, B, S, lo, cnt, ns, counts,
-                       nullptr, nullptr, nullptr, 0, first);
-  else if (out64)
-    hipLaunchKernelGGL((sorted_match_kernel<K2, int64_t, true, MASKED>), g, b, 0, stream, B, S, lo, cnt, ns, nullptr,
-                       offsets, static_cast<int64_t*>(sidx), static_cast<int64_t*>(bidx), out_cap, nullptr);
-  else
-    hipLaunchKernelGGL((sorted_match_kernel<K2, int32_t, true, MASKED>), g, b, 0, stream, B, S, lo, cnt, ns, nullptr,
-                       offsets, static_cast<int32_t*>(sidx), static_cast<int32_t*>(bidx), out_cap, nullptr);
+  if (!offsets) {
+    launch(what, sorted_match_kernel<K2, int32_t, false, MASKED>, g, b, 0, stream, as<K2>(big2), as<K2>(small2), lo,
+           cnt, ns, counts, nullptr, nullptr, nullptr, 0, first);
+    return;
+  }
+  dispatch(wide{out64}, [&](auto o) {
+    using O = type_of<decltype(o)>;
+    launch(what, sorted_match_kernel<K2, O, true, MASKED>, g, b, 0, stream, as<K2>(big2), as<K2>(small2), lo, cnt, ns,
+           nullptr, offsets, as<O>(sidx), as<O>(bidx), out_cap, nullptr);
+  });
 }
 
 }  // namespace
@@ -270,21 +265,17 @@ void sorted_match(const void* big2, const void* small2, bool key64, const int64_
                   int64_t ns, int32_t* counts, const int64_t* offsets, void* sidx, void* bidx, bool out64,
                   int64_t out_cap, int32_t* first, hipStream_t stream) {
   if (ns <= 0) return;
-  if (key64)
-    launch_match<int64_t, false>(big2, small2, lo, cnt, ns, counts, offsets, sidx, bidx, out64, out_cap, first,
-                                 stream);
-  else
-    launch_match<int32_t, false>(big2, small2, lo, cnt, ns, counts, offsets, sidx, bidx, out64, out_cap, first,
-                                 stream);
-  check_launch("sorted_match", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    launch_match<type_of<decltype(k)>, false>("sorted_match", big2, small2, lo, cnt, ns, counts, offsets, sidx, bidx,
+                                              out64, out_cap, first, stream);
+  });
 }
 
 void sorted_masked(const uint8_t* mask, const int64_t* lo, const int64_t* cnt, int64_t ns, int32_t* counts,
                    const int64_t* offsets, void* sidx, void* bidx, bool out64, int64_t out_cap, hipStream_t stream) {
   if (ns <= 0) return;
-  launch_match<int32_t, true>(mask, nullptr, lo, cnt, ns, counts, offsets, sidx, bidx, out64, out_cap, nullptr,
-                              stream);
-  check_launch("sorted_masked", stream);
+  launch_match<int32_t, true>("sorted_masked", mask, nullptr, lo, cnt, ns, counts, offsets, sidx, bidx, out64, out_cap,
+                              nullptr, stream);
 }
 
 }  // namespace kern
@@ -361,61 +352,37 @@ __global__ __launch_bounds__(kBlock) void dense_ranges_kernel(const I* __restric
   }
 }
 
-template <typename K>
-void dense_launch(bool build, const void* big, int64_t nb, int64_t kmin, int64_t kmax, void* first, bool first64,
-                  int32_t* long_gap, const void* q, const uint8_t* qvalid, int64_t nq, int64_t* lo, int64_t* cnt, hipStream_t stream) {
-  const dim3 b(kBlock);
-  if (build && !long_gap) {  // fix-up pass
-    const int64_t span = kmax - kmin + 1;
-    const dim3 g(grid_for(span + 1, kBlock, 1 << 16));
-    if (first64)
-      hipLaunchKernelGGL((dense_fill_kernel<K, int64_t>), g, b, 0, stream, static_cast<const K*>(big), nb, kmin, span,
-                         (int64_t)-1, static_cast<int64_t*>(first));
-    else
-      hipLaunchKernelGGL((dense_fill_kernel<K, int32_t>), g, b, 0, stream, static_cast<const K*>(big), nb, kmin, span,
-                         (int32_t)-1, static_cast<int32_t*>(first));
-  } else if (build) {
-    const dim3 g(grid_for(nb + 1, kBlock, 1 << 16));
-    if (first64)
-      hipLaunchKernelGGL((dense_index_kernel<K, int64_t>), g, b, 0, stream, static_cast<const K*>(big), nb, kmin, kmax,
-                         static_cast<int64_t*>(first), long_gap);
-    else
-      hipLaunchKernelGGL((dense_index_kernel<K, int32_t>), g, b, 0, stream, static_cast<const K*>(big), nb, kmin, kmax,
-                         static_cast<int32_t*>(first), long_gap);
-  } else {
-    const dim3 g(grid_for(nq, kBlock, 1 << 16));
-    if (first64)
-      hipLaunchKernelGGL((dense_ranges_kernel<K, int64_t>), g, b, 0, stream, static_cast<const int64_t*>(first), kmin,
-                         kmax, static_cast<const K*>(q), qvalid, nq, lo, cnt);
-    else
-      hipLaunchKernelGGL((dense_ranges_kernel<K, int32_t>), g, b, 0, stream, static_cast<const int32_t*>(first), kmin,
-                         kmax, static_cast<const K*>(q), qvalid, nq, lo, cnt);
-  }
-}
-
 }  // namespace
 
 void dense_index_build(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, void* first, bool first64,
                        int32_t* long_gap, hipStream_t stream) {
-  if (key64)
-    dense_launch<int64_t>(true, big, nb, kmin, kmax, first, first64, long_gap, nullptr, nullptr, 0, nullptr, nullptr,
-                          stream);
-  else
-    dense_launch<int32_t>(true, big, nb, kmin, kmax, first, first64, long_gap, nullptr, nullptr, 0, nullptr, nullptr,
-                          stream);
-  check_launch("dense_index_build", stream);
+  const dim3 b(kBlock);
+  dispatch(wide{key64}, wide{first64}, [&](auto k, auto i) {
+    using K = type_of<decltype(k)>;
+    using I = type_of<decltype(i)>;
+    if (!long_gap) {  // fix-up pass
+      const int64_t span = kmax - kmin + 1;
+      const dim3 g(grid_for(span + 1, kBlock, 1 << 16));
+      launch("dense_index_build", dense_fill_kernel<K, I>, g, b, 0, stream, as<K>(big), nb, kmin, span, (I)-1,
+             as<I>(first));
+    } else {
+      const dim3 g(grid_for(nb + 1, kBlock, 1 << 16));
+      launch("dense_index_build", dense_index_kernel<K, I>, g, b, 0, stream, as<K>(big), nb, kmin, kmax, as<I>(first),
+             long_gap);
+    }
+  });
 }
 
 void dense_ranges(const void* first, bool first64, int64_t kmin, int64_t kmax, const void* q, bool key64,
                   const uint8_t* qvalid, int64_t nq, int64_t* lo, int64_t* cnt, hipStream_t stream) {
   if (nq <= 0) return;
-  if (key64)
-    dense_launch<int64_t>(false, nullptr, 0, kmin, kmax, const_cast<void*>(first), first64, nullptr, q, qvalid, nq, lo,
-                          cnt, stream);
-  else
-    dense_launch<int32_t>(false, nullptr, 0, kmin, kmax, const_cast<void*>(first), first64, nullptr, q, qvalid, nq, lo,
-                          cnt, stream);
-  check_launch("dense_ranges", stream);
+  const dim3 g(grid_for(nq, kBlock, 1 << 16)), b(kBlock);
+  dispatch(wide{key64}, wide{first64}, [&](auto k, auto i) {
+    using K = type_of<decltype(k)>;
+    using I = type_of<decltype(i)>;
+    launch("dense_ranges", dense_ranges_kernel<K, I>, g, b, 0, stream, as<I>(first), kmin, kmax, as<K>(q), qvalid, nq,
+           lo, cnt);
+  });
 }
 
 }  // namespace kern
@@ -464,13 +431,11 @@ void sorted_exists(const void* big2, const void* small2, bool key64, const int64
                    int64_t ns, int op, const uint8_t* mask, uint8_t* hit, hipStream_t stream) {
   if (ns <= 0) return;
   const dim3 g(grid_for(ns, kBlock, 1 << 16)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(sorted_exists_kernel<int64_t>, g, b, 0, stream, (const int64_t*)big2, (const int64_t*)small2,
-                       lo, cnt, ns, op, mask, hit);
-  else
-    hipLaunchKernelGGL(sorted_exists_kernel<int32_t>, g, b, 0, stream, (const int32_t*)big2, (const int32_t*)small2,
-                       lo, cnt, ns, op, mask, hit);
-  check_launch("sorted_exists", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K2 = type_of<decltype(k)>;
+    launch("sorted_exists", sorted_exists_kernel<K2>, g, b, 0, stream, as<K2>(big2), as<K2>(small2), lo, cnt, ns, op,
+           mask, hit);
+  });
 }
 }  // namespace kern
 }  // namespace igloo
@@ -544,34 +509,18 @@ void unique_lookup(const void* big, bool key64, int64_t nb, const void* first, b
                    int64_t kmax, const void* q, const uint8_t* qvalid, int64_t nq, uint8_t* hit, int32_t* pos,
                    const void* fence, int64_t nf, hipStream_t stream) {
   if (nq <= 0) return;
-  const unsigned grid = grid_for(nq, kBlock, 1 << 16);
-  if (first) {
-    if (key64 && first64)
-      hipLaunchKernelGGL((unique_dense_kernel<int64_t, int64_t>), dim3(grid), dim3(kBlock), 0, stream,
-                         static_cast<const int64_t*>(first), kmin, kmax, static_cast<const int64_t*>(q), qvalid, nq,
-                         hit, pos);
-    else if (key64)
-      hipLaunchKernelGGL((unique_dense_kernel<int64_t, int32_t>), dim3(grid), dim3(kBlock), 0, stream,
-                         static_cast<const int32_t*>(first), kmin, kmax, static_cast<const int64_t*>(q), qvalid, nq,
-                         hit, pos);
-    else if (first64)
-      hipLaunchKernelGGL((unique_dense_kernel<int32_t, int64_t>), dim3(grid), dim3(kBlock), 0, stream,
-                         static_cast<const int64_t*>(first), kmin, kmax, static_cast<const int32_t*>(q), qvalid, nq,
-                         hit, pos);
-    else
-      hipLaunchKernelGGL((unique_dense_kernel<int32_t, int32_t>), dim3(grid), dim3(kBlock), 0, stream,
-                         static_cast<const int32_t*>(first), kmin, kmax, static_cast<const int32_t*>(q), qvalid, nq,
-                         hit, pos);
-  } else if (key64) {
-    hipLaunchKernelGGL(unique_search_kernel<int64_t>, dim3(grid), dim3(kBlock), 0, stream,
-                       static_cast<const int64_t*>(big), nb, static_cast<const int64_t*>(q), qvalid, nq, hit, pos,
-                       static_cast<const int64_t*>(fence), nf);
-  } else {
-    hipLaunchKernelGGL(unique_search_kernel<int32_t>, dim3(grid), dim3(kBlock), 0, stream,
-                       static_cast<const int32_t*>(big), nb, static_cast<const int32_t*>(q), qvalid, nq, hit, pos,
-                       static_cast<const int32_t*>(fence), nf);
-  }
-  check_launch("unique_lookup", stream);
+  const dim3 g(grid_for(nq, kBlock, 1 << 16)), b(kBlock);
+  dispatch(wide{key64}, wide{first64}, [&](auto k, auto i) {
+    using K = type_of<decltype(k)>;
+    using I = type_of<decltype(i)>;
+    if (first) {
+      launch("unique_lookup", unique_dense_kernel<K, I>, g, b, 0, stream, as<I>(first), kmin, kmax, as<K>(q), qvalid,
+             nq, hit, pos);
+    } else {
+      launch("unique_lookup", unique_search_kernel<K>, g, b, 0, stream, as<K>(big), nb, as<K>(q), qvalid, nq, hit, pos,
+             as<K>(fence), nf);
+    }
+  });
 }
 
 }  // namespace kern

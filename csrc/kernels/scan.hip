@@ -5,6 +5,7 @@
 // workgroups, and each phase streams the input once.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -127,15 +128,12 @@ void exclusive_scan_impl(const T* in, int64_t n, int64_t* out, int64_t* tile_ws,
     return;
   }
   if (n <= kSmall) {
-    hipLaunchKernelGGL(small_scan_kernel<T>, dim3(1), dim3(kBlock), 0, stream, in, n, out, total);
-    check_launch("scan.small", stream);
+    launch("scan.small", small_scan_kernel<T>, dim3(1), dim3(kBlock), 0, stream, in, n, out, total);
     return;
   }
-  hipLaunchKernelGGL(tile_sum_kernel<T>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, in, n, tile_ws);
-  check_launch("scan.tile_sum", stream);
+  launch("scan.tile_sum", tile_sum_kernel<T>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, in, n, tile_ws);
   scan_counts(tile_ws, tiles, total, stream);
-  hipLaunchKernelGGL(tile_scan_kernel<T>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, in, n, tile_ws, out);
-  check_launch("scan.tile_scan", stream);
+  launch("scan.tile_scan", tile_scan_kernel<T>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, in, n, tile_ws, out);
 }
 
 }  // namespace
@@ -144,10 +142,9 @@ int64_t scan_workspace_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
 
 void exclusive_scan(const void* in, bool in64, int64_t n, int64_t* out, int64_t* tile_ws, int64_t* total,
                     hipStream_t stream) {
-  if (in64)
-    exclusive_scan_impl((const int64_t*)in, n, out, tile_ws, total, stream);
-  else
-    exclusive_scan_impl((const int32_t*)in, n, out, tile_ws, total, stream);
+  dispatch(wide{in64}, [&](auto t) {
+    exclusive_scan_impl(as<type_of<decltype(t)>>(in), n, out, tile_ws, total, stream);
+  });
 }
 
 }  // namespace kern

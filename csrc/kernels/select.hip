@@ -20,6 +20,7 @@
 // ~73k workgroups: far more than 256 CUs x occupancy, as the HBM stream wants.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -274,9 +275,8 @@ void select_compact(const uint8_t* mask, int64_t n, const int64_t* tile_offsets,
                     hipStream_t stream) {
   int64_t tiles = select_num_tiles(n);
   if (tiles == 0) return;
-  hipLaunchKernelGGL(tile_compact_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, mask, n, tile_offsets, a,
-                     cap);
-  check_launch("select.compact", stream);
+  launch("select.compact", tile_compact_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, mask, n, tile_offsets,
+         a, cap);
 }
 
 int64_t select_num_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
@@ -289,33 +289,27 @@ void select_count(const uint8_t* mask, int64_t n, int64_t* tile_counts, int64_t*
     return;
   }
   if (tiles <= kSmallTiles) {
-    hipLaunchKernelGGL(small_count_kernel, dim3(1), dim3(kBlock), 0, stream, mask, n, (int)tiles, tile_counts, total);
-    check_launch("select.small_count", stream);
+    launch("select.small_count", small_count_kernel, dim3(1), dim3(kBlock), 0, stream, mask, n, (int)tiles, tile_counts,
+           total);
     return;
   }
-  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, mask, n,
-                     tile_counts);
-  check_launch("select.tile_count", stream);
-  hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, stream, tile_counts, tiles, total);
-  check_launch("select.scan", stream);
+  launch("select.tile_count", tile_count_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, stream, mask, n, tile_counts);
+  launch("select.scan", scan_counts_kernel, dim3(1), dim3(1024), 0, stream, tile_counts, tiles, total);
 }
 
 void select_write(const uint8_t* mask, int64_t n, const int64_t* tile_offsets, void* out, bool idx64, int64_t cap,
                   hipStream_t stream) {
   int64_t tiles = select_num_tiles(n);
   if (tiles == 0) return;
-  if (idx64)
-    hipLaunchKernelGGL(tile_write_kernel<int64_t>, dim3((unsigned)tiles), dim3(kBlock), 0, stream,
-                       mask, n, tile_offsets, (int64_t*)out, cap);
-  else
-    hipLaunchKernelGGL(tile_write_kernel<int32_t>, dim3((unsigned)tiles), dim3(kBlock), 0, stream,
-                       mask, n, tile_offsets, (int32_t*)out, cap);
-  check_launch("select.tile_write", stream);
+  dispatch(wide{idx64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    launch("select.tile_write", tile_write_kernel<I>, dim3((unsigned)tiles), dim3(kBlock), 0, stream, mask, n,
+           tile_offsets, as<I>(out), cap);
+  });
 }
 
 void scan_counts(int64_t* counts, int64_t n, int64_t* total, hipStream_t stream) {
-  hipLaunchKernelGGL(scan_counts_kernel, dim3(1), dim3(1024), 0, stream, counts, n, total);
-  check_launch("scan_counts", stream);
+  launch("scan_counts", scan_counts_kernel, dim3(1), dim3(1024), 0, stream, counts, n, total);
 }
 
 }  // namespace kern

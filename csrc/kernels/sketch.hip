@@ -12,6 +12,7 @@
 // No global atomics, so the grid can be sized to fill all 256 CUs.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -61,13 +62,12 @@ int hll_blocks(int64_t n) {
 void hll_sketch(const void* keys, bool key64, const uint8_t* valid, int64_t n, uint8_t* block_regs, uint8_t* regs,
                 hipStream_t stream) {
   int blocks = hll_blocks(n);
-  if (key64)
-    hll_block_kernel<int64_t><<<blocks, kBlock, 0, stream>>>((const int64_t*)keys, valid, n, block_regs);
-  else
-    hll_block_kernel<int32_t><<<blocks, kBlock, 0, stream>>>((const int32_t*)keys, valid, n, block_regs);
-  check_launch("hll_block", stream);
-  hll_reduce_kernel<<<(kHllRegisters + kBlock - 1) / kBlock, kBlock, 0, stream>>>(block_regs, blocks, regs);
-  check_launch("hll_reduce", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("hll_block", hll_block_kernel<K>, dim3(blocks), dim3(kBlock), 0, stream, as<K>(keys), valid, n, block_regs);
+  });
+  launch("hll_reduce", hll_reduce_kernel, dim3((kHllRegisters + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
+         block_regs, blocks, regs);
 }
 
 }  // namespace kern

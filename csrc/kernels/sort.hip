@@ -23,6 +23,7 @@
 //   workgroup launch doing every pass in LDS.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -452,30 +453,25 @@ int64_t radix_sort_ws_bytes(int64_t n) {
 
 int radix_sort_pairs(void* k0, void* k1, bool key64, void* v0, void* v1, bool val64, int64_t n, int begin_bit,
                      int end_bit, void* ws, hipStream_t stream) {
-  uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  if (key64) {
-    if (val64)
-      return radix_sort_impl((uint64_t*)k0, (uint64_t*)k1, (int64_t*)v0, (int64_t*)v1, n, begin_bit, end_bit, w, stream);
-    return radix_sort_impl((uint64_t*)k0, (uint64_t*)k1, (int32_t*)v0, (int32_t*)v1, n, begin_bit, end_bit, w, stream);
-  }
-  if (val64)
-    return radix_sort_impl((uint32_t*)k0, (uint32_t*)k1, (int64_t*)v0, (int64_t*)v1, n, begin_bit, end_bit, w, stream);
-  return radix_sort_impl((uint32_t*)k0, (uint32_t*)k1, (int32_t*)v0, (int32_t*)v1, n, begin_bit, end_bit, w, stream);
+  int cur = 0;
+  dispatch(uwide{key64}, wide{val64}, [&](auto k, auto v) {
+    using K = type_of<decltype(k)>;
+    using V = type_of<decltype(v)>;
+    cur = radix_sort_impl(as<K>(k0), as<K>(k1), as<V>(v0), as<V>(v1), n, begin_bit, end_bit, as<uint8_t>(ws), stream);
+  });
+  return cur;
 }
 
 void sort_key_pack(const SortKeySpec& spec, const void* perm, bool perm64, int64_t n, void* out, bool out32,
                    hipStream_t stream) {
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock, 8192);
-#define IGLOO_PACK(P, O) \
-  hipLaunchKernelGGL((sort_key_pack_kernel<P, O>), dim3(g), dim3(kBlock), 0, stream, spec, (const P*)perm, n, (O*)out)
-  if (perm64) {
-    if (out32) IGLOO_PACK(int64_t, uint32_t); else IGLOO_PACK(int64_t, uint64_t);
-  } else {
-    if (out32) IGLOO_PACK(int32_t, uint32_t); else IGLOO_PACK(int32_t, uint64_t);
-  }
-#undef IGLOO_PACK
-  check_launch("sort.key_pack", stream);
+  dispatch(wide{perm64}, uwide{!out32}, [&](auto p, auto o) {
+    using P = type_of<decltype(p)>;
+    using O = type_of<decltype(o)>;
+    launch("sort.key_pack", sort_key_pack_kernel<P, O>, dim3(g), dim3(kBlock), 0, stream, spec, as<P>(perm), n,
+           as<O>(out));
+  });
 }
 
 void radix_digit_hist(const void* keys, bool key64, int64_t n, int shift, uint64_t prefix, int pshift,
@@ -483,25 +479,20 @@ void radix_digit_hist(const void* keys, bool key64, int64_t n, int shift, uint64
   hipLaunchKernelGGL(rs_zero_hist_kernel, dim3(1), dim3(kRadix), 0, stream, hist, kRadix);
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock * 8, 2048);
-  if (key64)
-    hipLaunchKernelGGL(rs_digit_hist_kernel<uint64_t>, dim3(g), dim3(kBlock), 0, stream, (const uint64_t*)keys, n,
-                       shift, prefix, pshift, hist);
-  else
-    hipLaunchKernelGGL(rs_digit_hist_kernel<uint32_t>, dim3(g), dim3(kBlock), 0, stream, (const uint32_t*)keys, n,
-                       shift, prefix, pshift, hist);
-  check_launch("sort.digit_hist", stream);
+  dispatch(uwide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("sort.digit_hist", rs_digit_hist_kernel<K>, dim3(g), dim3(kBlock), 0, stream, as<K>(keys), n, shift, prefix,
+           pshift, hist);
+  });
 }
 
 void radix_le_mask(const void* keys, bool key64, int64_t n, uint64_t bound, uint8_t* mask, hipStream_t stream) {
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock * 8, 8192);
-  if (key64)
-    hipLaunchKernelGGL(rs_le_mask_kernel<uint64_t>, dim3(g), dim3(kBlock), 0, stream, (const uint64_t*)keys, n, bound,
-                       mask);
-  else
-    hipLaunchKernelGGL(rs_le_mask_kernel<uint32_t>, dim3(g), dim3(kBlock), 0, stream, (const uint32_t*)keys, n, bound,
-                       mask);
-  check_launch("sort.le_mask", stream);
+  dispatch(uwide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("sort.le_mask", rs_le_mask_kernel<K>, dim3(g), dim3(kBlock), 0, stream, as<K>(keys), n, bound, mask);
+  });
 }
 
 }  // namespace kern

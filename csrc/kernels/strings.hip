@@ -12,6 +12,7 @@
 //   GROUP BY, join verification and predicates on plain string columns.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -795,13 +796,11 @@ void str_eq_rows(const int64_t* aoff, const uint8_t* achars, const void* ai, con
                  const void* bi, bool idx64, int64_t n, int* mismatches, hipStream_t stream) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, 65536)), b(kBlock);
-  if (idx64)
-    hipLaunchKernelGGL(eq_rows_kernel<int64_t>, g, b, 0, stream, aoff, achars, (const int64_t*)ai, boff, bchars,
-                       (const int64_t*)bi, n, mismatches);
-  else
-    hipLaunchKernelGGL(eq_rows_kernel<int32_t>, g, b, 0, stream, aoff, achars, (const int32_t*)ai, boff, bchars,
-                       (const int32_t*)bi, n, mismatches);
-  check_launch("str_eq_rows", stream);
+  dispatch(wide{idx64}, [&](auto i) {
+    using I = type_of<decltype(i)>;
+    launch("str_eq_rows", eq_rows_kernel<I>, g, b, 0, stream, aoff, achars, as<I>(ai), boff, bchars, as<I>(bi), n,
+           mismatches);
+  });
 }
 
 void str_cmp_const(const int64_t* off, const uint8_t* chars, int64_t n, const uint8_t* c, int64_t cn, int op,

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -177,21 +178,10 @@ void column_stats(const void* keys, bool key64, const uint8_t* valid, int64_t n,
     check_launch("util.column_stats", stream);
     return;
   }
-  if (key64) {
-    if (valid)
-      hipLaunchKernelGGL((column_stats_kernel<int64_t, true>), dim3(g), dim3(kBlock), 0, stream, (const int64_t*)keys,
-                         valid, n, part);
-    else
-      hipLaunchKernelGGL((column_stats_kernel<int64_t, false>), dim3(g), dim3(kBlock), 0, stream, (const int64_t*)keys,
-                         valid, n, part);
-  } else {
-    if (valid)
-      hipLaunchKernelGGL((column_stats_kernel<int32_t, true>), dim3(g), dim3(kBlock), 0, stream, (const int32_t*)keys,
-                         valid, n, part);
-    else
-      hipLaunchKernelGGL((column_stats_kernel<int32_t, false>), dim3(g), dim3(kBlock), 0, stream, (const int32_t*)keys,
-                         valid, n, part);
-  }
+  dispatch(wide{key64}, valid != nullptr, [&](auto k, auto v) {
+    using K = type_of<decltype(k)>;
+    hipLaunchKernelGGL((column_stats_kernel<K, v.value>), dim3(g), dim3(kBlock), 0, stream, as<K>(keys), valid, n, part);
+  });
   hipLaunchKernelGGL(stats_reduce_kernel, dim3(1), dim3(kBlock), 0, stream, part, (int)g, out);
   check_launch("util.column_stats", stream);
 }
@@ -199,11 +189,10 @@ void column_stats(const void* keys, bool key64, const uint8_t* valid, int64_t n,
 void run_bounds(const void* keys, bool key64, int64_t n, uint8_t* out, hipStream_t stream) {
   if (n <= 0) return;
   const unsigned g = grid_for(n, kBlock * 4, 8192);
-  if (key64)
-    hipLaunchKernelGGL(run_bounds_kernel<int64_t>, dim3(g), dim3(kBlock), 0, stream, (const int64_t*)keys, n, out);
-  else
-    hipLaunchKernelGGL(run_bounds_kernel<int32_t>, dim3(g), dim3(kBlock), 0, stream, (const int32_t*)keys, n, out);
-  check_launch("util.run_bounds", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("util.run_bounds", run_bounds_kernel<K>, dim3(g), dim3(kBlock), 0, stream, as<K>(keys), n, out);
+  });
 }
 
 namespace {
@@ -272,19 +261,19 @@ void differs_from_rep(const void* a, int elem_bytes, const void* rep, bool rep64
   hipLaunchKernelGGL(zero_flag_kernel, dim3(1), dim3(1), 0, stream, flag);
   if (n > 0) {
     const dim3 g(grid_for(n, kBlock * 4, 8192)), b(kBlock);
-#define IGLOO_DIFF(T)                                                                                      \
-  if (rep64)                                                                                               \
-    hipLaunchKernelGGL((differs_from_rep_kernel<T, int64_t>), g, b, 0, stream, (const T*)a, (const int64_t*)rep, n, \
-                       flag);                                                                              \
-  else                                                                                                     \
-    hipLaunchKernelGGL((differs_from_rep_kernel<T, int32_t>), g, b, 0, stream, (const T*)a, (const int32_t*)rep, n, flag);
+    const auto diff = [&](auto t) {
+      using T = type_of<decltype(t)>;
+      dispatch(wide{rep64}, [&](auto r) {
+        using R = type_of<decltype(r)>;
+        hipLaunchKernelGGL((differs_from_rep_kernel<T, R>), g, b, 0, stream, as<T>(a), as<R>(rep), n, flag);
+      });
+    };
     switch (elem_bytes) {
-      case 1: IGLOO_DIFF(uint8_t) break;
-      case 2: IGLOO_DIFF(uint16_t) break;
-      case 4: IGLOO_DIFF(uint32_t) break;
-      default: IGLOO_DIFF(uint64_t) break;
+      case 1: diff(tag<uint8_t>{}); break;
+      case 2: diff(tag<uint16_t>{}); break;
+      case 4: diff(tag<uint32_t>{}); break;
+      default: diff(tag<uint64_t>{}); break;
     }
-#undef IGLOO_DIFF
   }
   check_launch("util.differs_from_rep", stream);
 }
@@ -464,24 +453,20 @@ void mark_keys(const void* keys, bool key64, const uint8_t* valid, int64_t n, in
                uint8_t* marks, hipStream_t stream) {
   if (n == 0) return;
   const dim3 g(grid_for(n, kBlock, 65536)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(mark_keys_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, valid, n, kmin, dom, marks);
-  else
-    hipLaunchKernelGGL(mark_keys_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, valid, n, kmin, dom, marks);
-  check_launch("mark_keys", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("mark_keys", mark_keys_kernel<K>, g, b, 0, stream, as<K>(keys), valid, n, kmin, dom, marks);
+  });
 }
 
 void probe_marks(const void* keys, bool key64, const uint8_t* valid, int64_t n, int64_t base, int64_t dom,
                  const uint8_t* marks, bool negate, uint8_t* out, hipStream_t stream) {
   if (n == 0) return;
   const dim3 g(grid_for(n, kBlock, 65536)), b(kBlock);
-  if (key64)
-    hipLaunchKernelGGL(probe_marks_kernel<int64_t>, g, b, 0, stream, (const int64_t*)keys, valid, n, base, dom, marks,
-                       negate, out);
-  else
-    hipLaunchKernelGGL(probe_marks_kernel<int32_t>, g, b, 0, stream, (const int32_t*)keys, valid, n, base, dom, marks,
-                       negate, out);
-  check_launch("probe_marks", stream);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("probe_marks", probe_marks_kernel<K>, g, b, 0, stream, as<K>(keys), valid, n, base, dom, marks, negate, out);
+  });
 }
 
 // End a stream capture the runtime invalidated (the failed capture's graph

@@ -26,6 +26,7 @@
 // Cargo.lock datafusion-functions-window 48.0.0).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace igloo {
 namespace kern {
@@ -682,14 +683,10 @@ void win_frame_minmax(const int64_t* vals, bool f64, bool is_max, const uint8_t*
                       const int64_t* hi, int64_t n, int64_t* out, uint8_t* out_valid, hipStream_t s) {
   if (n == 0) return;
   dim3 g(grid_for(n, kBlock, INT32_MAX)), b(kBlock);
-  if (f64) {
-    if (is_max) hipLaunchKernelGGL((win_frame_minmax_kernel<true, true>), g, b, 0, s, vals, valid, lo, hi, n, out, out_valid);
-    else hipLaunchKernelGGL((win_frame_minmax_kernel<true, false>), g, b, 0, s, vals, valid, lo, hi, n, out, out_valid);
-  } else {
-    if (is_max) hipLaunchKernelGGL((win_frame_minmax_kernel<false, true>), g, b, 0, s, vals, valid, lo, hi, n, out, out_valid);
-    else hipLaunchKernelGGL((win_frame_minmax_kernel<false, false>), g, b, 0, s, vals, valid, lo, hi, n, out, out_valid);
-  }
-  check_launch("win.frame_minmax", s);
+  dispatch(f64, is_max, [&](auto f, auto mx) {
+    launch("win.frame_minmax", win_frame_minmax_kernel<f.value, mx.value>, g, b, 0, s, vals, valid, lo, hi, n, out,
+           out_valid);
+  });
 }
 
 void win_rank(int fn, int64_t arg, int64_t n, const int64_t* seg_start, const int64_t* seg_end,
