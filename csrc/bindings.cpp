@@ -2,6 +2,10 @@
 // device runtime. Pointer arguments are passed as integers (torch
 // tensor.data_ptr()); shape/dtype validation happens in igloo_amd/ops before
 // any launch, so this layer is a thin, allocation-free trampoline.
+// A launcher that needs nothing but those casts is bound as raw<&kern::name>:
+// the adaptor deduces the signature from kernels.h, takes uintptr_t for every
+// pointer (hipStream_t included) and casts it back to the launcher's own type.
+// Bindings that check, build an argument or release the GIL stay lambdas.
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -25,6 +29,36 @@ T* P(uintptr_t p) {
   return reinterpret_cast<T*>(p);
 }
 hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// raw<&f>: f with each pointer parameter taken as uintptr_t; all else unchanged
+template <typename T>
+struct py_arg {
+  using type = T;
+  static T get(T v) { return v; }
+};
+template <typename T>
+struct py_arg<T*> {
+  using type = uintptr_t;
+  static T* get(uintptr_t v) { return reinterpret_cast<T*>(v); }
+};
+template <auto F>
+struct raw_t;
+template <typename R, typename... A, R (*F)(A...)>
+struct raw_t<F> {
+  R operator()(typename py_arg<A>::type... a) const { return F(py_arg<A>::get(a)...); }
+};
+template <auto F>
+constexpr raw_t<F> raw{};
+
+// the (op, src64, src, valid, dst, dst2) list of the aggregate bindings
+using AggDescArg = std::vector<std::tuple<int, int, uintptr_t, uintptr_t, uintptr_t, uintptr_t>>;
+std::vector<kern::AggDesc> agg_descs(const AggDescArg& descs) {
+  std::vector<kern::AggDesc> d;
+  for (auto& t : descs)
+    d.push_back({std::get<0>(t), std::get<1>(t), P<const void>(std::get<2>(t)), P<const uint8_t>(std::get<3>(t)),
+                 P<void>(std::get<4>(t)), P<void>(std::get<5>(t))});
+  return d;
+}
 
 py::list parse(const std::string& text) {
   py::list out;
@@ -174,6 +208,30 @@ PYBIND11_MODULE(_native, m) {
 
   // ------------------------------------------------------- select / scan
   m.def("select_num_tiles", &kern::select_num_tiles);
+  m.def("select_count", raw<&kern::select_count>);
+  // tile counts a fused scan wrote with its mask -> exclusive offsets in place + total
+  m.def("select_scan_counts", [](uintptr_t counts, int64_t tiles, uintptr_t total, uintptr_t s) {
+    if (!counts || !total || tiles <= 0) throw std::runtime_error("select_scan_counts: bad arguments");
+    kern::scan_counts(P<int64_t>(counts), tiles, P<int64_t>(total), S(s));
+  });
+  m.def("select_write", raw<&kern::select_write>);
+  m.def("select_compact", [](uintptr_t mask, int64_t n, uintptr_t tiles,
+                             const std::vector<std::tuple<uintptr_t, uintptr_t, int, uintptr_t, uintptr_t>>& cols,
+                             uintptr_t idx, bool idx64, int64_t cap, uintptr_t s) {
+    kern::CompactArgs a{};
+    if ((int)cols.size() > kern::kMaxCompactCols) throw std::runtime_error("select_compact: too many columns");
+    for (size_t j = 0; j < cols.size(); ++j) {
+      auto& c = cols[j];
+      a.cols[j] = {P<void>(std::get<0>(c)), P<void>(std::get<1>(c)), std::get<2>(c), P<uint8_t>(std::get<3>(c)),
+                   P<uint8_t>(std::get<4>(c))};
+    }
+    a.ncols = (int)cols.size();
+    a.idx = P<void>(idx);
+    a.idx64 = idx64;
+    kern::select_compact(P<uint8_t>(mask), n, P<int64_t>(tiles), a, cap, S(s));
+  });
+  m.def("scan_workspace_tiles", &kern::scan_workspace_tiles);
+  m.def("exclusive_scan", raw<&kern::exclusive_scan>);
   // ---- pack.hip
   auto pack_spec = [](const std::vector<std::tuple<uintptr_t, uintptr_t, int, int>>& cols, int row_bytes) {
     if (cols.size() > (size_t)kern::kMaxPackCols) throw std::runtime_error("pack: too many columns");
@@ -198,19 +256,31 @@ PYBIND11_MODULE(_native, m) {
     kern::unpack_rows(pack_spec(cols, row_bytes), P<const uint8_t>(in), n, S(s));
   });
   // ---- util.hip
-  m.def("column_stats", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::column_stats(P<const void>(keys), key64, P<const uint8_t>(valid), n, P<long long>(out), S(s));
+  m.def("column_stats", raw<&kern::column_stats>);
+  m.def("run_bounds", raw<&kern::run_bounds>);
+  m.def("mark_slot_rows", raw<&kern::mark_slot_rows>);
+  m.def("pack_bits", [](std::vector<uintptr_t> cols, std::vector<bool> is64, std::vector<int64_t> lo,
+                        std::vector<int> shift, int64_t n, uintptr_t out, uintptr_t s) {
+    std::vector<const void*> c(cols.size());
+    std::unique_ptr<bool[]> w(new bool[cols.size()]);
+    for (size_t i = 0; i < cols.size(); ++i) {
+      c[i] = reinterpret_cast<const void*>(cols[i]);
+      w[i] = is64[i];
+    }
+    kern::pack_bits(c.data(), w.get(), lo.data(), shift.data(), (int)cols.size(), n, P<int64_t>(out), S(s));
   });
-  m.def("run_bounds", [](uintptr_t keys, bool key64, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::run_bounds(P<const void>(keys), key64, n, P<uint8_t>(out), S(s));
+  m.def("differs_from_rep", raw<&kern::differs_from_rep>);
+  m.def("mark_keys", raw<&kern::mark_keys>);
+  m.def("probe_marks", raw<&kern::probe_marks>);
+  m.def("const_ints", [](uintptr_t out, std::vector<int64_t> vals, uintptr_t s) {
+    kern::const_ints(P<int64_t>(out), vals.data(), (int64_t)vals.size(), S(s));
   });
+  m.def("end_capture", raw<&kern::end_capture>);
+  m.def("wide_fits", raw<&kern::wide_fits>);
+  m.def("avg_wide", raw<&kern::avg_wide>);
   // ---- sort.hip
   m.def("radix_sort_ws_bytes", &kern::radix_sort_ws_bytes);
-  m.def("radix_sort_pairs", [](uintptr_t k0, uintptr_t k1, bool key64, uintptr_t v0, uintptr_t v1, bool val64,
-                               int64_t n, int begin_bit, int end_bit, uintptr_t ws, uintptr_t s) {
-    return kern::radix_sort_pairs(P<void>(k0), P<void>(k1), key64, P<void>(v0), P<void>(v1), val64, n, begin_bit,
-                                  end_bit, P<void>(ws), S(s));
-  });
+  m.def("radix_sort_pairs", raw<&kern::radix_sort_pairs>);
   m.def("sort_key_pack", [](std::vector<std::tuple<uintptr_t, uintptr_t, uint64_t, uint64_t, int, int, int, int, int>> cols,
                             uintptr_t perm, bool perm64, int64_t n, uintptr_t out, bool out32, uintptr_t s) {
     if (cols.empty() || cols.size() > (size_t)kern::kMaxSortCols) throw std::runtime_error("sort_key_pack: bad column count");
@@ -235,44 +305,8 @@ PYBIND11_MODULE(_native, m) {
     if (total > (out32 ? 32 : 64)) throw std::runtime_error("sort_key_pack: key fields exceed the key width");
     kern::sort_key_pack(spec, P<const void>(perm), perm64, n, P<void>(out), out32, S(s));
   });
-  m.def("radix_digit_hist", [](uintptr_t keys, bool key64, int64_t n, int shift, uint64_t prefix, int pshift,
-                               uintptr_t hist, uintptr_t s) {
-    kern::radix_digit_hist(P<const void>(keys), key64, n, shift, prefix, pshift, P<unsigned long long>(hist), S(s));
-  });
-  m.def("radix_le_mask", [](uintptr_t keys, bool key64, int64_t n, uint64_t bound, uintptr_t mask, uintptr_t s) {
-    kern::radix_le_mask(P<const void>(keys), key64, n, bound, P<uint8_t>(mask), S(s));
-  });
-  m.def("select_count", [](uintptr_t mask, int64_t n, uintptr_t tiles, uintptr_t total, uintptr_t s) {
-    kern::select_count(P<const uint8_t>(mask), n, P<int64_t>(tiles), P<int64_t>(total), S(s));
-  });
-  // tile counts a fused scan wrote with its mask -> exclusive offsets in place + total
-  m.def("select_scan_counts", [](uintptr_t counts, int64_t tiles, uintptr_t total, uintptr_t s) {
-    if (!counts || !total || tiles <= 0) throw std::runtime_error("select_scan_counts: bad arguments");
-    kern::scan_counts(P<int64_t>(counts), tiles, P<int64_t>(total), S(s));
-  });
-  m.def("select_write", [](uintptr_t mask, int64_t n, uintptr_t tiles, uintptr_t out, bool idx64, int64_t cap,
-                           uintptr_t s) {
-    kern::select_write(P<const uint8_t>(mask), n, P<const int64_t>(tiles), P<void>(out), idx64, cap, S(s));
-  });
-  m.def("select_compact", [](uintptr_t mask, int64_t n, uintptr_t tiles,
-                             const std::vector<std::tuple<uintptr_t, uintptr_t, int, uintptr_t, uintptr_t>>& cols,
-                             uintptr_t idx, bool idx64, int64_t cap, uintptr_t s) {
-    kern::CompactArgs a{};
-    if ((int)cols.size() > kern::kMaxCompactCols) throw std::runtime_error("select_compact: too many columns");
-    for (size_t j = 0; j < cols.size(); ++j) {
-      auto& c = cols[j];
-      a.cols[j] = {P<void>(std::get<0>(c)), P<void>(std::get<1>(c)), std::get<2>(c), P<uint8_t>(std::get<3>(c)),
-                   P<uint8_t>(std::get<4>(c))};
-    }
-    a.ncols = (int)cols.size();
-    a.idx = P<void>(idx);
-    a.idx64 = idx64;
-    kern::select_compact(P<uint8_t>(mask), n, P<int64_t>(tiles), a, cap, S(s));
-  });
-  m.def("scan_workspace_tiles", &kern::scan_workspace_tiles);
-  m.def("exclusive_scan", [](uintptr_t in, bool in64, int64_t n, uintptr_t out, uintptr_t ws, uintptr_t total, uintptr_t s) {
-    kern::exclusive_scan(P<const void>(in), in64, n, P<int64_t>(out), P<int64_t>(ws), P<int64_t>(total), S(s));
-  });
+  m.def("radix_digit_hist", raw<&kern::radix_digit_hist>);
+  m.def("radix_le_mask", raw<&kern::radix_le_mask>);
 
   // ------------------------------------------------------------ hash tables
   m.def("join_build", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t tkeys, uintptr_t thead,
@@ -306,7 +340,7 @@ PYBIND11_MODULE(_native, m) {
                      P<const void>(thead), P<const void>(cstart), P<const void>(crows), rid64, cap, kmin, direct,
                      P<int32_t>(counts), P<void>(first), P<uint8_t>(matched), P<const uint32_t>(bits), bmask, S(s));
   });
-  m.def("probe_hit_tiles", [](int64_t m_) { return kern::probe_hit_tiles(m_); });
+  m.def("probe_hit_tiles", &kern::probe_hit_tiles);
   m.def("probe_hits", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
                          bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t bits, uint64_t bmask,
                          bool negate, int64_t n_build, uintptr_t fold, uintptr_t words, uintptr_t tile_counts,
@@ -431,75 +465,63 @@ PYBIND11_MODULE(_native, m) {
     f.overflow = P<int>(overflow);
     kern::ff_aggregate(f, n, S(s));
   });
-  m.def("ff_set_mfma", [](bool on) { return kern::ff_set_mfma(on); });
+  m.def("ff_set_mfma", &kern::ff_set_mfma);
   m.attr("HLL_REGISTERS") = kern::kHllRegisters;
-  m.def("hll_blocks", [](int64_t n) { return kern::hll_blocks(n); });
-  m.def("hll_sketch", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t block_regs, uintptr_t regs,
-                         uintptr_t s) {
-    kern::hll_sketch(P<const void>(keys), key64, P<const uint8_t>(valid), n, P<uint8_t>(block_regs),
-                     P<uint8_t>(regs), S(s));
-  });
-  m.def("groupby_build", [](uintptr_t keys, bool key64, int64_t n, uintptr_t tkeys, uintptr_t trow, int64_t cap,
-                            int64_t kmin, bool direct, uintptr_t s) {
-    kern::groupby_build(P<const void>(keys), key64, n, P<int64_t>(tkeys), P<int32_t>(trow), cap, kmin, direct, S(s));
-  });
-  m.def("groupby_occupied", [](uintptr_t trow, int64_t cap, uintptr_t occ, uintptr_t gid_of_slot, uintptr_t s) {
-    kern::groupby_occupied(P<const int32_t>(trow), cap, P<uint8_t>(occ), P<int32_t>(gid_of_slot), S(s));
-  });
-  m.def("groupby_assign", [](uintptr_t slots, bool slots64, int64_t g, int64_t cap, uintptr_t trow,
-                             uintptr_t gid_of_slot, uintptr_t rep_row, uintptr_t s) {
-    kern::groupby_assign(P<const void>(slots), slots64, g, cap, P<const int32_t>(trow), P<int32_t>(gid_of_slot),
-                         P<int32_t>(rep_row), S(s));
-  });
-  m.def("groupby_lookup", [](uintptr_t keys, bool key64, int64_t n, uintptr_t tkeys, uintptr_t gid_of_slot,
-                             int64_t cap, int64_t kmin, bool direct, uintptr_t gid, uintptr_t s) {
-    kern::groupby_lookup(P<const void>(keys), key64, n, P<const int64_t>(tkeys), P<const int32_t>(gid_of_slot), cap,
-                         kmin, direct, P<int32_t>(gid), S(s));
-  });
+  m.def("hll_blocks", &kern::hll_blocks);
+  m.def("hll_sketch", raw<&kern::hll_sketch>);
+  m.def("groupby_build", raw<&kern::groupby_build>);
+  m.def("groupby_occupied", raw<&kern::groupby_occupied>);
+  m.def("groupby_assign", raw<&kern::groupby_assign>);
+  m.def("groupby_lookup", raw<&kern::groupby_lookup>);
+  m.def("fill_runs", raw<&kern::fill_runs>);
 
   // ------------------------------------------------------------ aggregation
   m.def("agg_lds_max_groups", &kern::agg_lds_max_groups);
   // descs: list of (op, src64, src, valid, dst, dst2)
-  m.def("agg_update", [](uintptr_t gid, int64_t n, int ngroups, const std::vector<std::tuple<int, int, uintptr_t, uintptr_t, uintptr_t, uintptr_t>>& descs, uintptr_t s, bool sorted_gids) {
-    std::vector<kern::AggDesc> d;
-    for (auto& t : descs)
-      d.push_back({std::get<0>(t), std::get<1>(t), P<const void>(std::get<2>(t)), P<const uint8_t>(std::get<3>(t)),
-                   P<void>(std::get<4>(t)), P<void>(std::get<5>(t))});
+  m.def("agg_update", [](uintptr_t gid, int64_t n, int ngroups, const AggDescArg& descs, uintptr_t s,
+                         bool sorted_gids) {
+    auto d = agg_descs(descs);
     kern::agg_update(P<const int32_t>(gid), n, ngroups, d.data(), (int)d.size(), S(s), sorted_gids);
   }, py::arg("gid"), py::arg("n"), py::arg("ngroups"), py::arg("descs"), py::arg("s"), py::arg("sorted_gids") = false);
-  m.def("agg_part_buckets", [](int64_t ngroups, int nagg) { return kern::agg_part_buckets(ngroups, nagg); });
-  m.def("agg_part_blocks", []() { return kern::agg_part_blocks(); });
+  m.def("agg_part_buckets", &kern::agg_part_buckets);
+  m.def("agg_part_blocks", &kern::agg_part_blocks);
   // phase 0 / 1 / 2 of the radix-partitioned aggregate; vals: one pointer per desc (0: COUNT(*))
-  m.def("agg_partitioned", [](uintptr_t gid, int64_t n, int64_t ngroups,
-                              const std::vector<std::tuple<int, int, uintptr_t, uintptr_t, uintptr_t, uintptr_t>>& descs,
-                              int phase, uintptr_t cnt, uintptr_t off, uintptr_t total, uintptr_t pg,
+  m.def("agg_partitioned", [](uintptr_t gid, int64_t n, int64_t ngroups, const AggDescArg& descs, int phase,
+                              uintptr_t cnt, uintptr_t off, uintptr_t total, uintptr_t pg,
                               const std::vector<uintptr_t>& vals, uintptr_t s) {
     if (!gid || n >= (int64_t(1) << 31) || ngroups <= 0 || ngroups >= (int64_t(1) << 31) || phase < 0 || phase > 2 ||
         descs.empty() || descs.size() > 8 || vals.size() != descs.size() || (phase == 0 && !cnt) ||
         (phase >= 1 && (!off || !pg)) || (phase == 2 && !total))
       throw std::runtime_error("agg_partitioned: bad arguments");
-    std::vector<kern::AggDesc> d;
-    for (auto& t : descs)
-      d.push_back({std::get<0>(t), std::get<1>(t), P<const void>(std::get<2>(t)), P<const uint8_t>(std::get<3>(t)),
-                   P<void>(std::get<4>(t)), P<void>(std::get<5>(t))});
+    auto d = agg_descs(descs);
     std::vector<int64_t*> v;
     for (auto x : vals) v.push_back(P<int64_t>(x));
     kern::agg_partitioned(P<const int32_t>(gid), n, ngroups, d.data(), (int)d.size(), phase, P<int32_t>(cnt),
                           P<const int64_t>(off), P<const int64_t>(total), P<uint16_t>(pg), v.data(), S(s));
   });
-  m.def("sorted_having", [](uintptr_t keys, bool key64, int64_t n,
-                            const std::vector<std::tuple<int, int, uintptr_t, uintptr_t, uintptr_t, uintptr_t>>& descs,
-                            int hagg, int hop, long long hlo, long long hhi, double hf, uintptr_t rep, int64_t cap,
-                            uintptr_t counter, uintptr_t s) {
-    std::vector<kern::AggDesc> d;
-    for (auto& t : descs)
-      d.push_back({std::get<0>(t), std::get<1>(t), P<const void>(std::get<2>(t)), P<const uint8_t>(std::get<3>(t)),
-                   P<void>(std::get<4>(t)), P<void>(std::get<5>(t))});
+  m.def("sorted_having", [](uintptr_t keys, bool key64, int64_t n, const AggDescArg& descs, int hagg, int hop,
+                            long long hlo, long long hhi, double hf, uintptr_t rep, int64_t cap, uintptr_t counter,
+                            uintptr_t s) {
+    auto d = agg_descs(descs);
     kern::sorted_having(P<const void>(keys), key64, n, d.data(), (int)d.size(), hagg, hop, hlo, hhi, hf,
                         P<int64_t>(rep), cap, P<unsigned long long>(counter), S(s));
   });
-  m.def("fill_runs", [](uintptr_t starts, bool starts64, int64_t nruns, int64_t n, uintptr_t gid, uintptr_t s) {
-    kern::fill_runs(P<const void>(starts), starts64, nruns, n, P<int32_t>(gid), S(s));
+  m.def("key_histogram", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t kmin, int64_t span,
+                            uintptr_t counts, uintptr_t s) {
+    if (n > 0 && (!keys || !counts || span <= 0)) throw std::runtime_error("key_histogram: bad arguments");
+    kern::key_histogram(P<const void>(keys), key64, P<const uint8_t>(valid), n, kmin, span, P<int32_t>(counts), S(s));
+  });
+  m.def("key_histogram_buckets", &kern::key_histogram_buckets);
+  m.def("key_histogram_blocks", &kern::key_histogram_blocks);
+  m.def("key_histogram_partitioned", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t kmin,
+                                        int64_t span, int phase, uintptr_t cnt, uintptr_t off, int64_t total,
+                                        uintptr_t part, uintptr_t counts, uintptr_t s) {
+    if (span <= 0 || span > (int64_t(1) << 27) || n >= (int64_t(1) << 31) || phase < 0 || phase > 2 || !keys ||
+        (phase == 0 && !cnt) || (phase >= 1 && (!off || !part)) || (phase == 2 && !counts))
+      throw std::runtime_error("key_histogram_partitioned: bad arguments");
+    kern::key_histogram_partitioned(P<const void>(keys), key64, P<const uint8_t>(valid), n, kmin, span, phase,
+                                    P<int32_t>(cnt), P<const int64_t>(off), total, P<uint16_t>(part),
+                                    P<int32_t>(counts), S(s));
   });
 
   // ----------------------------------------------------------------- gather
@@ -519,112 +541,24 @@ PYBIND11_MODULE(_native, m) {
     kern::gather_packed(P<const void>(idx), idx64, n, P<const uint8_t>(src), rows, row_bytes, f.data(), (int)f.size(),
                         S(s));
   });
-  m.def("str_gather_lengths", [](uintptr_t off, int64_t rows, uintptr_t idx, bool idx64, int64_t n, uintptr_t len,
-                                 uintptr_t s) {
-    kern::str_gather_lengths(P<const int64_t>(off), rows, P<const void>(idx), idx64, n, P<int64_t>(len), S(s));
-  });
-  m.def("str_gather_copy", [](uintptr_t off, int64_t rows, uintptr_t chars, uintptr_t idx, bool idx64, int64_t n,
-                              uintptr_t new_off, uintptr_t out, int64_t out_cap, uintptr_t s) {
-    kern::str_gather_copy(P<const int64_t>(off), rows, P<const uint8_t>(chars), P<const void>(idx), idx64, n,
-                          P<const int64_t>(new_off), P<uint8_t>(out), out_cap, S(s));
-  });
+  m.def("str_gather_lengths", raw<&kern::str_gather_lengths>);
+  m.def("str_gather_copy", raw<&kern::str_gather_copy>);
 
   // ---------------------------------------------------------------- strings
-  m.def("str_like", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t pat, uintptr_t kind, int mlen, bool ci,
-                       bool neg, uintptr_t out, uintptr_t s) {
-    kern::str_like(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(pat), P<const uint8_t>(kind),
-                   mlen, ci, neg, P<uint8_t>(out), S(s));
-  });
-  m.def("str_case", [](uintptr_t in, int64_t nbytes, bool up, uintptr_t out, uintptr_t flag, uintptr_t s) {
-    kern::str_case(P<const uint8_t>(in), nbytes, up, P<uint8_t>(out), P<int>(flag), S(s));
-  });
-  m.def("str_substr_lengths", [](uintptr_t off, uintptr_t chars, int64_t n, int64_t start, int64_t len, bool has_len,
-                                 uintptr_t out, uintptr_t s) {
-    kern::str_substr_lengths(P<const int64_t>(off), P<const uint8_t>(chars), n, start, len, has_len, P<int64_t>(out), S(s));
-  });
-  m.def("str_substr_copy", [](uintptr_t off, uintptr_t chars, int64_t n, int64_t start, int64_t len, bool has_len,
-                              uintptr_t new_off, uintptr_t out, uintptr_t s) {
-    kern::str_substr_copy(P<const int64_t>(off), P<const uint8_t>(chars), n, start, len, has_len,
-                          P<const int64_t>(new_off), P<uint8_t>(out), S(s));
-  });
-  m.def("mark_slot_rows", [](uintptr_t trow, int64_t cap, int64_t n, uintptr_t mark, uintptr_t s) {
-    kern::mark_slot_rows(P<const int32_t>(trow), cap, n, P<uint8_t>(mark), S(s));
-  });
-  m.def("pack_bits", [](std::vector<uintptr_t> cols, std::vector<bool> is64, std::vector<int64_t> lo,
-                        std::vector<int> shift, int64_t n, uintptr_t out, uintptr_t s) {
-    std::vector<const void*> c(cols.size());
-    std::unique_ptr<bool[]> w(new bool[cols.size()]);
-    for (size_t i = 0; i < cols.size(); ++i) {
-      c[i] = reinterpret_cast<const void*>(cols[i]);
-      w[i] = is64[i];
-    }
-    kern::pack_bits(c.data(), w.get(), lo.data(), shift.data(), (int)cols.size(), n, P<int64_t>(out), S(s));
-  });
-  m.def("differs_from_rep", [](uintptr_t a, int elem_bytes, uintptr_t rep, bool rep64, int64_t n, uintptr_t flag,
-                               uintptr_t s) {
-    kern::differs_from_rep(P<const void>(a), elem_bytes, P<const void>(rep), rep64, n, P<int>(flag), S(s));
-  });
-  m.def("mark_keys", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t kmin, int64_t dom,
-                        uintptr_t marks, uintptr_t s) {
-    kern::mark_keys(P<const void>(keys), key64, P<const uint8_t>(valid), n, kmin, dom, P<uint8_t>(marks), S(s));
-  });
-  m.def("probe_marks", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t base, int64_t dom,
-                          uintptr_t marks, bool negate, uintptr_t out, uintptr_t s) {
-    kern::probe_marks(P<const void>(keys), key64, P<const uint8_t>(valid), n, base, dom, P<const uint8_t>(marks),
-                      negate, P<uint8_t>(out), S(s));
-  });
-  m.def("const_ints", [](uintptr_t out, std::vector<int64_t> vals, uintptr_t s) {
-    kern::const_ints(P<int64_t>(out), vals.data(), (int64_t)vals.size(), S(s));
-  });
-  m.def("end_capture", [](uintptr_t s) { kern::end_capture(S(s)); });
-  m.def("str_char_length", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::str_char_length(P<const int64_t>(off), P<const uint8_t>(chars), n, P<int32_t>(out), S(s));
-  });
-  m.def("str_concat2_lengths", [](uintptr_t oa, bool ba, uintptr_t ob, bool bb, int64_t n, uintptr_t len, uintptr_t s) {
-    kern::str_concat2_lengths(P<const int64_t>(oa), ba, P<const int64_t>(ob), bb, n, P<int64_t>(len), S(s));
-  });
-  m.def("str_concat2_copy", [](uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
-                               uintptr_t off, uintptr_t out, uintptr_t s) {
-    kern::str_concat2_copy(P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob), P<const uint8_t>(cb),
-                           bb, n, P<const int64_t>(off), P<uint8_t>(out), S(s));
-  });
-  m.def("fmt_lengths", [](uintptr_t vals, int kind, int64_t n, int scale, uintptr_t valid, uintptr_t len, uintptr_t s) {
-    kern::fmt_lengths(P<const void>(vals), kind, n, scale, P<const uint8_t>(valid), P<int64_t>(len), S(s));
-  });
-  m.def("fmt_write", [](uintptr_t vals, int kind, int64_t n, int scale, uintptr_t valid, uintptr_t off, uintptr_t out,
-                        uintptr_t s) {
-    kern::fmt_write(P<const void>(vals), kind, n, scale, P<const uint8_t>(valid), P<const int64_t>(off), P<uint8_t>(out),
-                    S(s));
-  });
-  m.def("str_parse", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t valid, int kind, int scale, uintptr_t out,
-                        uintptr_t err, uintptr_t s) {
-    kern::str_parse(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(valid), kind, scale,
-                    P<void>(out), P<int>(err), S(s));
-  });
-  m.def("wide_fits", [](uintptr_t lo, uintptr_t hi, int64_t n, uintptr_t flag, uintptr_t s) {
-    kern::wide_fits(P<const int64_t>(lo), P<const int64_t>(hi), n, P<int>(flag), S(s));
-  });
-  m.def("avg_wide", [](uintptr_t sums, bool wide, uintptr_t cnt, int64_t n, int64_t up, uintptr_t out, uintptr_t s) {
-    kern::avg_wide(P<const int64_t>(sums), wide, P<const int64_t>(cnt), n, up, P<int64_t>(out), S(s));
-  });
-  m.def("str_prefix_keys", [](uintptr_t off, uintptr_t chars, int64_t n, int chunks, uintptr_t out, uintptr_t s) {
-    kern::str_prefix_keys(P<const int64_t>(off), P<const uint8_t>(chars), n, chunks, P<int64_t>(out), S(s));
-  });
-  m.def("str_hash64", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t valid, uintptr_t out, uintptr_t s) {
-    kern::str_hash64(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(valid), P<int64_t>(out), S(s));
-  });
-  m.def("str_like_segments", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t seg, uintptr_t seg_off, int nseg,
-                                 bool anchor_start, bool anchor_end, bool negate, uintptr_t out, int64_t nbytes,
-                                 int min_seg, uintptr_t s) {
-    kern::str_like_segments(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(seg),
-                            P<const int32_t>(seg_off), nseg, anchor_start, anchor_end, negate, P<uint8_t>(out), nbytes,
-                            min_seg, S(s));
-  });
-  m.def("str_eq_rows", [](uintptr_t aoff, uintptr_t achars, uintptr_t ai, uintptr_t boff, uintptr_t bchars, uintptr_t bi,
-                          bool idx64, int64_t n, uintptr_t mism, uintptr_t s) {
-    kern::str_eq_rows(P<const int64_t>(aoff), P<const uint8_t>(achars), P<const void>(ai), P<const int64_t>(boff),
-                      P<const uint8_t>(bchars), P<const void>(bi), idx64, n, P<int>(mism), S(s));
-  });
+  m.def("str_like", raw<&kern::str_like>);
+  m.def("str_case", raw<&kern::str_case>);
+  m.def("str_substr_lengths", raw<&kern::str_substr_lengths>);
+  m.def("str_substr_copy", raw<&kern::str_substr_copy>);
+  m.def("str_char_length", raw<&kern::str_char_length>);
+  m.def("str_concat2_lengths", raw<&kern::str_concat2_lengths>);
+  m.def("str_concat2_copy", raw<&kern::str_concat2_copy>);
+  m.def("fmt_lengths", raw<&kern::fmt_lengths>);
+  m.def("fmt_write", raw<&kern::fmt_write>);
+  m.def("str_parse", raw<&kern::str_parse>);
+  m.def("str_prefix_keys", raw<&kern::str_prefix_keys>);
+  m.def("str_hash64", raw<&kern::str_hash64>);
+  m.def("str_like_segments", raw<&kern::str_like_segments>);
+  m.def("str_eq_rows", raw<&kern::str_eq_rows>);
   m.def("str_in_set", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t vb, uintptr_t voff, uintptr_t vmode,
                          int nv, uintptr_t out, uintptr_t s) {
     if (n > 0 && (!off || !out || nv < 0 || (nv > 0 && (!vb || !voff || !vmode))))
@@ -632,14 +566,8 @@ PYBIND11_MODULE(_native, m) {
     kern::str_in_set(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(vb), P<const int32_t>(voff),
                      P<const uint8_t>(vmode), nv, P<uint8_t>(out), S(s));
   });
-  m.def("str_cmp_const", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t c, int64_t cn, int op, uintptr_t out,
-                            uintptr_t s) {
-    kern::str_cmp_const(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint8_t>(c), cn, op,
-                        P<uint8_t>(out), S(s));
-  });
-  m.def("str_prefix_key", [](uintptr_t off, uintptr_t chars, int64_t n, int64_t skip, uintptr_t out, uintptr_t s) {
-    kern::str_prefix_key(P<const int64_t>(off), P<const uint8_t>(chars), n, skip, P<int64_t>(out), S(s));
-  });
+  m.def("str_cmp_const", raw<&kern::str_cmp_const>);
+  m.def("str_prefix_key", raw<&kern::str_prefix_key>);
 
   // -------------------------------------------------------------------- csv
   m.attr("CSV_TILE") = kern::kCsvTile;
@@ -669,9 +597,7 @@ PYBIND11_MODULE(_native, m) {
     kern::csv_parse(P<const uint8_t>(buf), start, P<const int64_t>(rows_end), nrows,
                     P<const kern::CsvColumn>(cols), ncols, (uint8_t)delim, (uint8_t)quote, P<int>(err), S(s));
   });
-  m.def("csv_str_lengths", [](uintptr_t len_flag, int64_t n, uintptr_t len, uintptr_t s) {
-    kern::csv_str_lengths(P<const int64_t>(len_flag), n, P<int64_t>(len), S(s));
-  });
+  m.def("csv_str_lengths", raw<&kern::csv_str_lengths>);
   m.def("csv_str_copy", [](uintptr_t pos, uintptr_t len_flag, uintptr_t off, int64_t n, int quote, uintptr_t out,
                            uintptr_t s) {
     kern::csv_str_copy(P<const int64_t>(pos), P<const int64_t>(len_flag), P<const int64_t>(off), n, (uint8_t)quote,
@@ -689,13 +615,7 @@ PYBIND11_MODULE(_native, m) {
                        P<const int64_t>(off), out_cap, P<uint8_t>(out), S(s));
   });
   m.def("regex_lds_bytes", &kern::regex_lds_bytes);
-  m.def("regex_dfa_match", [](uintptr_t off, uintptr_t chars, int64_t n, uintptr_t table, uintptr_t cls,
-                              uintptr_t flags, int nstates, int nclasses, int start, bool anchored_end, bool negate,
-                              uintptr_t out, uintptr_t s) {
-    kern::regex_dfa_match(P<const int64_t>(off), P<const uint8_t>(chars), n, P<const uint16_t>(table),
-                          P<const uint8_t>(cls), P<const uint8_t>(flags), nstates, nclasses, start, anchored_end,
-                          negate, P<uint8_t>(out), S(s));
-  });
+  m.def("regex_dfa_match", raw<&kern::regex_dfa_match>);
   // span automaton as (table, cls, flags, nstates, nclasses, anchored_start, anchored_end)
   using SpanDfaArg = std::tuple<uintptr_t, uintptr_t, uintptr_t, int, int, bool, bool>;
   auto span_dfa = [](const SpanDfaArg& d) {
@@ -720,11 +640,7 @@ PYBIND11_MODULE(_native, m) {
     kern::regex_span_replace(span_dfa(d), P<const int64_t>(off), P<const uint8_t>(chars), n, all,
                              P<const uint8_t>(repl), repl_len, P<const int64_t>(new_off), P<uint8_t>(out), cap, S(s));
   });
-  m.def("probe_hash16", [](bool mfma, uintptr_t k0, uintptr_t k1, uintptr_t k2, uintptr_t k3, int64_t n,
-                           uintptr_t proj, uintptr_t out, uintptr_t s) {
-    kern::probe_hash16(mfma, P<const int32_t>(k0), P<const int32_t>(k1), P<const int32_t>(k2), P<const int32_t>(k3),
-                       n, P<const int8_t>(proj), P<uint32_t>(out), S(s));
-  });
+  m.def("probe_hash16", raw<&kern::probe_hash16>);
   m.def("probe_inlist16", [](bool mfma, uintptr_t off, uintptr_t chars, int64_t n, const std::string& pats, int npat,
                              int len, uintptr_t out, uintptr_t s) {
     if ((int64_t)pats.size() < 16 * npat) throw std::runtime_error("probe_inlist16: 16 bytes per pattern");
@@ -732,166 +648,46 @@ PYBIND11_MODULE(_native, m) {
                          reinterpret_cast<const uint8_t*>(pats.data()), npat, len, P<uint8_t>(out), S(s));
   });
   m.def("digest_width", &kern::digest_width);
-  m.def("digest_hex", [](int algo, uintptr_t off, uintptr_t chars, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::digest_hex(algo, P<const int64_t>(off), P<const uint8_t>(chars), n, P<uint8_t>(out), S(s));
-  });
-  m.def("bin_hex_encode", [](uintptr_t in, int64_t nbytes, uintptr_t out, uintptr_t s) {
-    kern::bin_hex_encode(P<const uint8_t>(in), nbytes, P<uint8_t>(out), S(s));
-  });
-  m.def("bin_hex_validate", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes, uintptr_t err,
-                               uintptr_t s) {
-    kern::bin_hex_validate(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
-                           P<int64_t>(err), S(s));
-  });
-  m.def("bin_hex_decode", [](uintptr_t off, int64_t n, uintptr_t in, int64_t nout, uintptr_t out, uintptr_t s) {
-    kern::bin_hex_decode(P<const int64_t>(off), n, P<const uint8_t>(in), nout, P<uint8_t>(out), S(s));
-  });
-  m.def("bin_b64_enc_lengths", [](uintptr_t off, uintptr_t valid, int64_t n, uintptr_t lens, uintptr_t s) {
-    kern::bin_b64_enc_lengths(P<const int64_t>(off), P<const uint8_t>(valid), n, P<int64_t>(lens), S(s));
-  });
-  m.def("bin_b64_dec_lengths", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes,
-                                  uintptr_t lens, uintptr_t err, uintptr_t s) {
-    kern::bin_b64_dec_lengths(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
-                              P<int64_t>(lens), P<int64_t>(err), S(s));
-  });
-  m.def("bin_b64_write", [](bool encode, uintptr_t ioff, uintptr_t chars, uintptr_t ooff, int64_t n,
-                            int64_t out_cap, uintptr_t out, uintptr_t s) {
-    kern::bin_b64_write(encode, P<const int64_t>(ioff), P<const uint8_t>(chars), P<const int64_t>(ooff), n,
-                        out_cap, P<uint8_t>(out), S(s));
-  });
+  m.def("digest_hex", raw<&kern::digest_hex>);
+  m.def("bin_hex_encode", raw<&kern::bin_hex_encode>);
+  m.def("bin_hex_validate", raw<&kern::bin_hex_validate>);
+  m.def("bin_hex_decode", raw<&kern::bin_hex_decode>);
+  m.def("bin_b64_enc_lengths", raw<&kern::bin_b64_enc_lengths>);
+  m.def("bin_b64_dec_lengths", raw<&kern::bin_b64_dec_lengths>);
+  m.def("bin_b64_write", raw<&kern::bin_b64_write>);
   m.def("utf8_num_tiles", &kern::utf8_num_tiles);
-  m.def("utf8_validate", [](uintptr_t off, uintptr_t chars, uintptr_t valid, int64_t n, int64_t nbytes, uintptr_t flags,
-                            uintptr_t err, uintptr_t s) {
-    kern::utf8_validate(P<const int64_t>(off), P<const uint8_t>(chars), P<const uint8_t>(valid), n, nbytes,
-                        P<uint8_t>(flags), P<int64_t>(err), S(s));
-  });
-  m.def("uuid_v4", [](uint64_t seed, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::uuid_v4(seed, n, P<uint8_t>(out), S(s));
-  });
-  m.def("list_element_idx", [](uintptr_t se, uintptr_t valid, uintptr_t pos, uintptr_t pos_valid, int64_t pos_const,
-                               int64_t n, int64_t child_n, uintptr_t out, uintptr_t s) {
-    kern::list_element_idx(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(pos),
-                           P<const uint8_t>(pos_valid), pos_const, n, child_n, P<int64_t>(out), S(s));
-  });
-  m.def("interleave_idx", [](int64_t n, int k, uintptr_t out, uintptr_t s) {
-    kern::interleave_idx(n, k, P<int64_t>(out), S(s));
-  });
-  m.def("list_slots", [](int64_t n, int64_t k, uintptr_t se, uintptr_t s) {
-    kern::list_slots(n, k, P<int64_t>(se), S(s));
-  });
+  m.def("utf8_validate", raw<&kern::utf8_validate>);
+  m.def("uuid_v4", raw<&kern::uuid_v4>);
+  m.def("list_element_idx", raw<&kern::list_element_idx>);
+  m.def("interleave_idx", raw<&kern::interleave_idx>);
+  m.def("list_slots", raw<&kern::list_slots>);
   m.attr("LIST_FAST_MAX") = (int)kern::kListFastMax;
-  m.def("map_lookup_idx", [](uintptr_t se, uintptr_t valid, int64_t n, int64_t child_n, int key_width, uintptr_t keys,
-                             uintptr_t kvalid, uintptr_t needle, uintptr_t needle_valid, int64_t needle_const,
-                             uintptr_t out, uintptr_t s) {
-    kern::map_lookup_idx(P<const int64_t>(se), P<const uint8_t>(valid), n, child_n, key_width, P<const void>(keys),
-                         P<const uint8_t>(kvalid), P<const int64_t>(needle), P<const uint8_t>(needle_valid),
-                         needle_const, P<int64_t>(out), S(s));
-  });
-  m.def("map_lookup_idx_str", [](uintptr_t se, uintptr_t valid, int64_t n, int64_t child_n, uintptr_t key_offs,
-                                 uintptr_t key_bytes, int64_t key_nbytes, uintptr_t kvalid, uintptr_t needle_offs,
-                                 uintptr_t needle_bytes, int64_t needle_nbytes, uintptr_t needle_valid,
-                                 int64_t const_len, int64_t const_stride, uintptr_t out, uintptr_t s) {
-    kern::map_lookup_idx_str(P<const int64_t>(se), P<const uint8_t>(valid), n, child_n, P<const int64_t>(key_offs),
-                             P<const uint8_t>(key_bytes), key_nbytes, P<const uint8_t>(kvalid),
-                             P<const int64_t>(needle_offs), P<const uint8_t>(needle_bytes), needle_nbytes,
-                             P<const uint8_t>(needle_valid), const_len, const_stride, P<int64_t>(out), S(s));
-  });
-  m.def("list_slice_se", [](uintptr_t se, uintptr_t valid, uintptr_t from, uintptr_t from_valid, uintptr_t to,
-                            uintptr_t to_valid, int64_t from_const, int64_t to_const, int64_t n, uintptr_t out_se,
-                            uintptr_t out_valid, uintptr_t s) {
-    kern::list_slice_se(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(from),
-                        P<const uint8_t>(from_valid), P<const int64_t>(to), P<const uint8_t>(to_valid), from_const,
-                        to_const, n, P<int64_t>(out_se), P<uint8_t>(out_valid), S(s));
-  });
-  m.def("list_parts_count", [](uintptr_t parts, int k, int64_t n, uintptr_t out_len, uintptr_t s) {
-    kern::list_parts_count(P<const int64_t>(parts), k, n, P<int64_t>(out_len), S(s));
-  });
-  m.def("list_parts_write", [](uintptr_t parts, int k, int64_t n, uintptr_t offs, int64_t src_n, int64_t cap,
-                               uintptr_t idx, uintptr_t out_se, uintptr_t s) {
-    kern::list_parts_write(P<const int64_t>(parts), k, n, P<const int64_t>(offs), src_n, cap, P<int64_t>(idx),
-                           P<int64_t>(out_se), S(s));
-  });
-  m.def("list_flatten_count", [](uintptr_t se, uintptr_t valid, uintptr_t ise, uintptr_t ivalid, int64_t n,
-                                 int64_t inner_n, uintptr_t out_len, uintptr_t s) {
-    kern::list_flatten_count(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(ise),
-                             P<const uint8_t>(ivalid), n, inner_n, P<int64_t>(out_len), S(s));
-  });
-  m.def("list_flatten_write", [](uintptr_t se, uintptr_t valid, uintptr_t ise, uintptr_t ivalid, int64_t n,
-                                 int64_t inner_n, uintptr_t offs, int64_t child_n, int64_t cap, uintptr_t idx,
-                                 uintptr_t out_se, uintptr_t s) {
-    kern::list_flatten_write(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(ise),
-                             P<const uint8_t>(ivalid), n, inner_n, P<const int64_t>(offs), child_n, cap,
-                             P<int64_t>(idx), P<int64_t>(out_se), S(s));
-  });
-  m.def("list_match_count", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
-                               uintptr_t needle, uintptr_t needle_valid, uintptr_t from, uintptr_t limit,
-                               int64_t limit_const, int mode, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::list_match_count(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
-                           P<const uint8_t>(kvalid), child_n, P<const int64_t>(needle),
-                           P<const uint8_t>(needle_valid), P<const int64_t>(from), P<const int64_t>(limit),
-                           limit_const, mode, n, P<int64_t>(out), S(s));
-  });
-  m.def("list_match_write", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
-                               uintptr_t needle, uintptr_t needle_valid, uintptr_t limit, int64_t limit_const,
-                               int mode, int64_t n, uintptr_t offs, int64_t repl_base, int64_t cap, uintptr_t out,
-                               uintptr_t s) {
-    kern::list_match_write(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
-                           P<const uint8_t>(kvalid), child_n, P<const int64_t>(needle),
-                           P<const uint8_t>(needle_valid), P<const int64_t>(limit), limit_const, mode, n,
-                           P<const int64_t>(offs), repl_base, cap, P<int64_t>(out), S(s));
-  });
-  m.def("list_minmax_idx", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
-                              int is_max, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::list_minmax_idx(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
-                          P<const uint8_t>(kvalid), child_n, is_max, n, P<int64_t>(out), S(s));
-  });
-  m.def("list_set_count", [](uintptr_t seA, uintptr_t validA, uintptr_t keysA, uintptr_t kvalidA, int64_t childA_n,
-                             uintptr_t seB, uintptr_t validB, uintptr_t keysB, uintptr_t kvalidB, int64_t childB_n,
-                             int op, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::list_set_count(P<const int64_t>(seA), P<const uint8_t>(validA), P<const int64_t>(keysA),
-                         P<const uint8_t>(kvalidA), childA_n, P<const int64_t>(seB), P<const uint8_t>(validB),
-                         P<const int64_t>(keysB), P<const uint8_t>(kvalidB), childB_n, op, n, P<int64_t>(out), S(s));
-  });
-  m.def("list_set_write", [](uintptr_t seA, uintptr_t validA, uintptr_t keysA, uintptr_t kvalidA, int64_t childA_n,
-                             uintptr_t seB, uintptr_t validB, uintptr_t keysB, uintptr_t kvalidB, int64_t childB_n,
-                             int op, int64_t n, uintptr_t offs, int64_t b_base, int64_t cap, uintptr_t idx,
-                             uintptr_t s) {
-    kern::list_set_write(P<const int64_t>(seA), P<const uint8_t>(validA), P<const int64_t>(keysA),
-                         P<const uint8_t>(kvalidA), childA_n, P<const int64_t>(seB), P<const uint8_t>(validB),
-                         P<const int64_t>(keysB), P<const uint8_t>(kvalidB), childB_n, op, n,
-                         P<const int64_t>(offs), b_base, cap, P<int64_t>(idx), S(s));
-  });
-  m.def("list_sort_idx", [](uintptr_t se, uintptr_t valid, uintptr_t keys, uintptr_t kvalid, int64_t child_n,
-                            int desc, int nulls_first, int64_t n, uintptr_t offs, int64_t cap, uintptr_t idx,
-                            uintptr_t s) {
-    kern::list_sort_idx(P<const int64_t>(se), P<const uint8_t>(valid), P<const int64_t>(keys),
-                        P<const uint8_t>(kvalid), child_n, desc, nulls_first, n, P<const int64_t>(offs), cap,
-                        P<int64_t>(idx), S(s));
-  });
+  m.def("map_lookup_idx", raw<&kern::map_lookup_idx>);
+  m.def("map_lookup_idx_str", raw<&kern::map_lookup_idx_str>);
+  m.def("list_slice_se", raw<&kern::list_slice_se>);
+  m.def("list_parts_count", raw<&kern::list_parts_count>);
+  m.def("list_parts_write", raw<&kern::list_parts_write>);
+  m.def("list_flatten_count", raw<&kern::list_flatten_count>);
+  m.def("list_flatten_write", raw<&kern::list_flatten_write>);
+  m.def("list_match_count", raw<&kern::list_match_count>);
+  m.def("list_match_write", raw<&kern::list_match_write>);
+  m.def("list_minmax_idx", raw<&kern::list_minmax_idx>);
+  m.def("list_set_count", raw<&kern::list_set_count>);
+  m.def("list_set_write", raw<&kern::list_set_write>);
+  m.def("list_sort_idx", raw<&kern::list_sort_idx>);
   m.def("json_parse", [](uintptr_t buf, int64_t start, uintptr_t rows_end, int64_t nrows, uintptr_t cols, int ncols,
                          uintptr_t names, uintptr_t name_off, uintptr_t err, uintptr_t s) {
     if (ncols > 64) throw std::runtime_error("json_parse: at most 64 fields");
     kern::json_parse(P<const uint8_t>(buf), start, P<const int64_t>(rows_end), nrows, P<const kern::CsvColumn>(cols),
                      ncols, P<const uint8_t>(names), P<const int32_t>(name_off), P<int>(err), S(s));
   });
-  m.def("json_str_copy", [](uintptr_t pos, uintptr_t len_flag, uintptr_t off, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::json_str_copy(P<const int64_t>(pos), P<const int64_t>(len_flag), P<const int64_t>(off), n, P<uint8_t>(out),
-                        S(s));
-  });
+  m.def("json_str_copy", raw<&kern::json_str_copy>);
 
   // ----------------------------------------------------------- sorted joins
-  m.def("sorted_ranges", [](uintptr_t big, bool key64, int64_t nb, uintptr_t q, uintptr_t qvalid, int64_t nq,
-                            uintptr_t lo, uintptr_t cnt, uintptr_t fence, int64_t nf, uintptr_t s) {
-    kern::sorted_ranges(P<const void>(big), key64, nb, P<const void>(q), P<const uint8_t>(qvalid), nq, P<int64_t>(lo),
-                        P<int64_t>(cnt), P<const void>(fence), nf, S(s));
-  });
+  m.def("sorted_ranges", raw<&kern::sorted_ranges>);
   m.attr("SEARCH_FENCE") = kern::kFence;
   m.attr("STATS_SLOTS") = kern::kStatsSlots;
-  m.def("expand_ranges", [](uintptr_t off, uintptr_t lo, int64_t ns, int64_t total, uintptr_t sidx, uintptr_t bidx,
-                            bool out64, uintptr_t s) {
-    kern::expand_ranges(P<const int64_t>(off), P<const int64_t>(lo), ns, total, P<void>(sidx), P<void>(bidx), out64,
-                        S(s));
-  });
+  m.def("expand_ranges", raw<&kern::expand_ranges>);
 
   m.def("dense_index_build", [](uintptr_t big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, uintptr_t first,
                                 bool first64, uintptr_t long_gap, uintptr_t s) {
@@ -913,23 +709,6 @@ PYBIND11_MODULE(_native, m) {
     kern::unique_lookup(P<const void>(big), key64, nb, P<const void>(first), first64, kmin, kmax, P<const void>(q),
                         P<const uint8_t>(qvalid), nq, P<uint8_t>(hit), P<int32_t>(pos), P<const void>(fence), nf,
                         S(s));
-  });
-  m.def("key_histogram", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t kmin, int64_t span,
-                            uintptr_t counts, uintptr_t s) {
-    if (n > 0 && (!keys || !counts || span <= 0)) throw std::runtime_error("key_histogram: bad arguments");
-    kern::key_histogram(P<const void>(keys), key64, P<const uint8_t>(valid), n, kmin, span, P<int32_t>(counts), S(s));
-  });
-  m.def("key_histogram_buckets", [](int64_t span) { return kern::key_histogram_buckets(span); });
-  m.def("key_histogram_blocks", []() { return kern::key_histogram_blocks(); });
-  m.def("key_histogram_partitioned", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, int64_t kmin,
-                                        int64_t span, int phase, uintptr_t cnt, uintptr_t off, int64_t total,
-                                        uintptr_t part, uintptr_t counts, uintptr_t s) {
-    if (span <= 0 || span > (int64_t(1) << 27) || n >= (int64_t(1) << 31) || phase < 0 || phase > 2 || !keys ||
-        (phase == 0 && !cnt) || (phase >= 1 && (!off || !part)) || (phase == 2 && !counts))
-      throw std::runtime_error("key_histogram_partitioned: bad arguments");
-    kern::key_histogram_partitioned(P<const void>(keys), key64, P<const uint8_t>(valid), n, kmin, span, phase,
-                                    P<int32_t>(cnt), P<const int64_t>(off), total, P<uint16_t>(part),
-                                    P<int32_t>(counts), S(s));
   });
   m.def("sorted_exists", [](uintptr_t big2, uintptr_t small2, bool key64, uintptr_t lo, uintptr_t cnt, int64_t ns,
                             int op, uintptr_t mask, uintptr_t hit, uintptr_t s) {
@@ -959,14 +738,9 @@ PYBIND11_MODULE(_native, m) {
 
   // -------------------------------------------------------------- partition
   m.def("partition_run_blocks", &kern::partition_run_blocks);
-  m.def("partition_run", [](uintptr_t keys, bool key64, int64_t n, int nparts, uintptr_t ws, uintptr_t total,
-                            uintptr_t perm, bool perm64, uintptr_t s) {
-    kern::partition_run(P<const void>(keys), key64, n, nparts, P<int64_t>(ws), P<int64_t>(total), P<void>(perm),
-                        perm64, S(s));
-  });
-  m.def("partition_ids", [](uintptr_t keys, bool key64, int64_t n, int nparts, uintptr_t out, uintptr_t s) {
-    kern::partition_ids(P<const void>(keys), key64, n, nparts, P<int32_t>(out), S(s));
-  });
+  m.def("partition_run", raw<&kern::partition_run>);
+  m.def("partition_ids", raw<&kern::partition_ids>);
+  m.def("date_part", raw<&kern::date_part>);
   m.def("str_fn_lengths", [](int fn, int64_t n1, uintptr_t a, int64_t alen, uintptr_t b, int64_t blen, uintptr_t off,
                              uintptr_t chars, int64_t n, uintptr_t len, uintptr_t s) {
     kern::StrFnArgs args{fn, n1, P<uint8_t>(a), alen, P<uint8_t>(b), blen};
@@ -979,73 +753,20 @@ PYBIND11_MODULE(_native, m) {
     kern::str_fn_copy(args, P<int64_t>(off), P<uint8_t>(chars), n, P<int64_t>(new_off), P<uint8_t>(out), out_cap,
                       S(s));
   });
-  m.def("str_fn_int", [](int fn, uintptr_t pat, int64_t plen, uintptr_t off, uintptr_t chars, int64_t n, uintptr_t out,
-                         uintptr_t s) {
-    kern::str_fn_int(fn, P<uint8_t>(pat), plen, P<int64_t>(off), P<uint8_t>(chars), n, P<int32_t>(out), S(s));
-  });
+  m.def("str_fn_int", raw<&kern::str_fn_int>);
   m.attr("LEV_FAST_MAX") = (int)kern::kLevFastMax;
-  m.def("str_pair_int", [](int fn, uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
-                           uintptr_t out, uintptr_t s) {
-    kern::str_pair_int(fn, P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob), P<const uint8_t>(cb),
-                       bb, n, P<int32_t>(out), S(s));
-  });
-  m.def("str_levenshtein", [](uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
-                              uintptr_t out, uintptr_t left, uintptr_t s) {
-    kern::str_levenshtein(P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob), P<const uint8_t>(cb),
-                          bb, n, P<int32_t>(out), P<int64_t>(left), S(s));
-  });
-  m.def("str_levenshtein_long", [](uintptr_t oa, uintptr_t ca, bool ba, uintptr_t ob, uintptr_t cb, bool bb, int64_t n,
-                                   uintptr_t out, uintptr_t scratch, int64_t lanes, int64_t cells, uintptr_t s) {
-    kern::str_levenshtein_long(P<const int64_t>(oa), P<const uint8_t>(ca), ba, P<const int64_t>(ob),
-                               P<const uint8_t>(cb), bb, n, P<int32_t>(out), P<int32_t>(scratch), lanes, cells, S(s));
-  });
+  m.def("str_pair_int", raw<&kern::str_pair_int>);
+  m.def("str_levenshtein", raw<&kern::str_levenshtein>);
+  m.def("str_levenshtein_long", raw<&kern::str_levenshtein_long>);
   m.def("win_scan_tiles", &kern::win_scan_tiles);
-  m.def("win_seg_scan", [](uintptr_t ids, bool ids64, uintptr_t ids2, bool ids2_64, uintptr_t vals, int vkind,
-                           uintptr_t valid, int64_t n, int op, bool reverse, uintptr_t tflag, uintptr_t tval,
-                           uintptr_t out, uintptr_t err, uintptr_t s) {
-    kern::win_seg_scan(P<void>(ids), ids64, P<void>(ids2), ids2_64, P<void>(vals), vkind, P<uint8_t>(valid), n, op,
-                       reverse, P<int>(tflag), P<int64_t>(tval), P<int64_t>(out), P<int>(err), S(s));
-  });
-  m.def("win_bounds", [](int64_t n, uintptr_t ss, uintptr_t se, uintptr_t ps, uintptr_t pe, int unit, int skind,
-                         int64_t soff_i, double soff_f, int ekind, int64_t eoff_i, double eoff_f, uintptr_t key,
-                         bool key_f64, uintptr_t key_valid, bool desc, uintptr_t gnum, uintptr_t gpos,
-                         int64_t ngroups, uintptr_t lo, uintptr_t hi, uintptr_t s) {
-    kern::win_bounds(n, P<int64_t>(ss), P<int64_t>(se), P<int64_t>(ps), P<int64_t>(pe), unit, skind, soff_i, soff_f,
-                     ekind, eoff_i, eoff_f, P<void>(key), key_f64, P<uint8_t>(key_valid), desc, P<int64_t>(gnum),
-                     P<int64_t>(gpos), ngroups, P<int64_t>(lo), P<int64_t>(hi), S(s));
-  });
-  m.def("win_frame_sum", [](uintptr_t psum, bool f64, uintptr_t pcnt, uintptr_t lo, uintptr_t hi, int64_t n,
-                            uintptr_t sum_out, uintptr_t cnt_out, uintptr_t s) {
-    kern::win_frame_sum(P<int64_t>(psum), f64, P<int64_t>(pcnt), P<int64_t>(lo), P<int64_t>(hi), n,
-                        P<int64_t>(sum_out), P<int64_t>(cnt_out), S(s));
-  });
-  m.def("win_sparse_build", [](uintptr_t vals, bool f64, uintptr_t valid, int64_t n, bool is_max, int levels,
-                               uintptr_t table, uintptr_t s) {
-    kern::win_sparse_build(P<int64_t>(vals), f64, P<uint8_t>(valid), n, is_max, levels, P<int64_t>(table), S(s));
-  });
-  m.def("win_sparse_query", [](uintptr_t table, int levels, int64_t n, uintptr_t lo, uintptr_t hi, uintptr_t pcnt,
-                               bool is_max, bool f64, uintptr_t out, uintptr_t out_valid, uintptr_t s) {
-    kern::win_sparse_query(P<int64_t>(table), levels, n, P<int64_t>(lo), P<int64_t>(hi), P<int64_t>(pcnt), is_max,
-                           f64, P<int64_t>(out), P<uint8_t>(out_valid), S(s));
-  });
-  m.def("win_frame_minmax", [](uintptr_t vals, bool f64, bool is_max, uintptr_t valid, uintptr_t lo, uintptr_t hi,
-                               int64_t n, uintptr_t out, uintptr_t out_valid, uintptr_t s) {
-    kern::win_frame_minmax(P<int64_t>(vals), f64, is_max, P<uint8_t>(valid), P<int64_t>(lo), P<int64_t>(hi), n,
-                           P<int64_t>(out), P<uint8_t>(out_valid), S(s));
-  });
-  m.def("win_rank", [](int fn, int64_t arg, int64_t n, uintptr_t ss, uintptr_t se, uintptr_t ps, uintptr_t pe,
-                       uintptr_t dense, uintptr_t out, uintptr_t s) {
-    kern::win_rank(fn, arg, n, P<int64_t>(ss), P<int64_t>(se), P<int64_t>(ps), P<int64_t>(pe), P<int64_t>(dense),
-                   P<int64_t>(out), S(s));
-  });
-  m.def("win_index", [](int fn, int64_t arg, int64_t n, uintptr_t ss, uintptr_t se, uintptr_t lo, uintptr_t hi,
-                        uintptr_t out, uintptr_t s) {
-    kern::win_index(fn, arg, n, P<int64_t>(ss), P<int64_t>(se), P<int64_t>(lo), P<int64_t>(hi), P<int64_t>(out),
-                    S(s));
-  });
-  m.def("date_part", [](uintptr_t days, int64_t n, int field, uintptr_t out, uintptr_t s) {
-    kern::date_part(P<const int32_t>(days), n, field, P<int32_t>(out), S(s));
-  });
+  m.def("win_seg_scan", raw<&kern::win_seg_scan>);
+  m.def("win_bounds", raw<&kern::win_bounds>);
+  m.def("win_frame_sum", raw<&kern::win_frame_sum>);
+  m.def("win_sparse_build", raw<&kern::win_sparse_build>);
+  m.def("win_sparse_query", raw<&kern::win_sparse_query>);
+  m.def("win_frame_minmax", raw<&kern::win_frame_minmax>);
+  m.def("win_rank", raw<&kern::win_rank>);
+  m.def("win_index", raw<&kern::win_index>);
 
   // ---------------------------------------------------------------- parquet
   m.def("pq_file_meta", [](const std::string& path) {
@@ -1149,9 +870,7 @@ PYBIND11_MODULE(_native, m) {
     kern::pq_decode(P<const kern::PqPage>(pages), npages, P<const int32_t>(page_col),
                     P<const kern::PqDecodeSpec>(specs), S(s));
   });
-  m.def("pq_str_copy", [](uintptr_t pos, uintptr_t off, int64_t n, uintptr_t out, uintptr_t s) {
-    kern::pq_str_copy(P<const int64_t>(pos), P<const int64_t>(off), n, P<uint8_t>(out), S(s));
-  });
+  m.def("pq_str_copy", raw<&kern::pq_str_copy>);
 
   // ---------------------------------------------------------------- datagen
   // params: (kind, seed, row_base, min_len, max_len, vocab, vocab_off, vocab_n,
