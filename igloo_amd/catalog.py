@@ -19,6 +19,7 @@ import torch
 from . import types as T
 from .columnar import Batch, Column
 from .types import DataType
+from .utils import tags
 from .utils.errors import PlanError
 
 
@@ -62,10 +63,7 @@ class TableSource:
 def _mark_resident(c: Column) -> None:
     """Flag a table column's data tensor as long-lived, so per-tensor derived
     structures (narrow copies for the fused scans) are worth building."""
-    try:
-        c.data._igloo_resident = True
-    except (AttributeError, RuntimeError):
-        pass
+    tags.RESIDENT.set(c.data, True)
 
 
 class MemoryTable(TableSource):

@@ -23,7 +23,7 @@ from ..ops import misc as M
 from ..ops import strings as S
 from ..ops._lib import (capturing, check_not_capturing, device_ints, launch, ptr, stream, to_host_f64s, to_host_int,
                        to_host_ints, unlogged)
-from ..utils import trace as _trace
+from ..utils import tags, trace as _trace
 from ..ops.gather import gather_tensor, take, take_many
 from ..ops.select import count_true, exclusive_scan, mask_to_indices
 from ..sql import logical as L
@@ -609,10 +609,7 @@ def aggregate(groups, aggs, b: Batch, ctx, row_parts: Optional[Dict[int, int]] =
                 and taken[0].valid is None and not taken[0].is_plain_string:
             # one row per group: a single key's values are distinct (a join
             # building on them skips its duplicate check, ops/hashing.py key_unique)
-            try:
-                taken[0].data._igloo_distinct = True
-            except (AttributeError, RuntimeError):
-                pass
+            tags.DISTINCT.set(taken[0].data, True)
     if late is not None and row_parts:
         for cid, k in row_parts.items():
             idx = b.parts[k][1]
@@ -636,20 +633,16 @@ def _full_key_hist(rcol: Column, kmin: int, span: int) -> Optional[torch.Tensor]
     """Rows per key of a resident NULL-free key column over [kmin, kmin +
     span), computed once and remembered on the column (None otherwise)."""
     t = rcol.data
-    if rcol.valid is not None or not getattr(t, "_igloo_resident", False) or not t.is_cuda:
+    if rcol.valid is not None or not tags.RESIDENT.get(t, False) or not t.is_cuda:
         return None
-    hit = getattr(t, "_igloo_key_hist", None)
+    hit = tags.KEY_HIST.get(t)
     if hit is not None and hit[0] == kmin and hit[1] == span:
         return hit[2]
     if capturing():
         return None
     with unlogged():     # a one-time build on a resident column (ops/_lib.py unlogged)
         h = A.key_histogram(t, kmin, span)
-    try:
-        t._igloo_key_hist = (kmin, span, h)
-    except (AttributeError, RuntimeError):
-        return None
-    return h
+    return h if tags.KEY_HIST.set(t, (kmin, span, h)) else None
 
 
 def _diff_bounds(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -22,7 +22,7 @@ from ..ops import misc as M
 from ..ops import strings as S
 from ..ops._lib import (check_not_capturing, device_ints, launch, ptr, stream, to_host_f64s, to_host_int,
                        to_host_ints, unlogged)
-from ..utils import trace as _trace
+from ..utils import tags, trace as _trace
 from ..ops.gather import gather_tensor, take, take_many
 from ..ops.select import exclusive_scan, mask_to_indices
 from ..sql import logical as L
@@ -115,7 +115,7 @@ class ExecContext:
 
     def note_partial_read(self, t: torch.Tensor, rows_read: int) -> None:
         """A join searched resident column ``t`` and touched only ``rows_read`` rows."""
-        if getattr(t, "_igloo_resident", False):
+        if tags.RESIDENT.get(t, False):
             self.rows_scanned -= max(0, t.numel() - rows_read)
 
     def span(self, name: str):

@@ -23,7 +23,7 @@ projection.rs:60-64, filter.rs:47-57).
 """
 from __future__ import annotations
 
-from ..utils import switches as _sw
+from ..utils import switches as _sw, tags
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -715,5 +715,5 @@ def evaluate(e: Expr, b: Batch, ev) -> object:
     if outv is None and out.dtype in (torch.int32, torch.int64) and (out_t.is_integer or out_t.is_decimal):
         rb = _raw_bound(e, b, out_t)
         if rb is not None:
-            out._igloo_bound = rb
+            tags.BOUND.set(out, rb)
     return Column(out_t, out, outv)

@@ -19,7 +19,7 @@ crates/engine/src/lib.rs:55-56; operators/filter.rs:47).
 """
 from __future__ import annotations
 
-from ..utils import switches as _sw
+from ..utils import switches as _sw, tags
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -304,9 +304,9 @@ def narrow(x: torch.Tensor) -> torch.Tensor:
     row instead of 8 (TPC-H Q1 reads l_quantity as int16, l_discount / l_tax
     as int8, l_extendedprice as int32). Other tensors are returned as is."""
     if not NARROW or x.dtype not in (torch.int32, torch.int64) or x.numel() < NARROW_MIN_ROWS \
-            or not getattr(x, "_igloo_resident", False):
+            or not tags.RESIDENT.get(x, False):
         return x
-    hit = getattr(x, "_igloo_narrow", None)
+    hit = tags.NARROW.get(x)
     if hit is None:
         check_not_capturing("narrow copy of a resident column")
         mn, mx = (int(v) for v in torch.aminmax(x))
@@ -317,9 +317,7 @@ def narrow(x: torch.Tensor) -> torch.Tensor:
             if torch.iinfo(t).min <= mn and mx <= torch.iinfo(t).max:
                 hit = x.to(t)
                 break
-        try:
-            x._igloo_narrow = hit
-        except (AttributeError, RuntimeError):
+        if not tags.NARROW.set(x, hit):
             return x
     return hit
 

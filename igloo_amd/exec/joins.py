@@ -22,7 +22,7 @@ from ..ops import misc as M
 from ..ops import strings as S
 from ..ops._lib import (check_not_capturing, device_ints, launch, ptr, stream, to_host_f64s, to_host_int,
                        to_host_ints, unlogged)
-from ..utils import trace as _trace
+from ..utils import tags, trace as _trace
 from ..ops.gather import gather_tensor, take, take_many
 from ..ops.select import count_true, exclusive_scan, mask_to_indices
 from ..sql import logical as L
@@ -97,7 +97,7 @@ def group_key_tensor(c: Column, narrow: bool = False) -> Tuple[torch.Tensor, Col
                 k = torch.where(d.valid, k, torch.full_like(k, -1))
         if nd is not None and k is not d.data:
             # codes index the dictionary: a readback-free key bound (ops/hashing.py key_bound)
-            k._igloo_bound = (-1 if d.valid is not None else 0, max(nd - 1, 0))
+            tags.BOUND.set(k, (-1 if d.valid is not None else 0, max(nd - 1, 0)))
         return k, d
     k = _num_key(c)
     if c.valid is not None:
@@ -222,7 +222,7 @@ def _index_key_filter(pk: torch.Tensor, bk: torch.Tensor, bvalid, ctx) -> Option
     probe fetches an L2 line per row for its bitmap bit). None when it does
     not apply."""
     n = pk.numel()
-    if not (ctx.device.type == "cuda" and PERM_INDEX and getattr(pk, "_igloo_resident", False)
+    if not (ctx.device.type == "cuda" and PERM_INDEX and tags.RESIDENT.get(pk, False)
             and n >= SORTED_JOIN_MIN_ROWS and PERM_INDEX_RATIO * bk.numel() <= n
             and bk.numel() * (n / _resident_ndv(pk)) * PERM_INDEX_SORT_FRAC <= n):
         return None
@@ -302,7 +302,7 @@ def _semi_index_scan(rnode, j, ctx):
     raw = rnode.peek_raw(ctx)
     rcol = raw.columns.get(names.get(re_.cid))
     if rcol is None or rcol.valid is not None or rcol.dtype.is_varlen or raw.num_rows < SORTED_JOIN_MIN_ROWS \
-            or not getattr(rcol.data, "_igloo_resident", False) or not H.is_sorted(rcol.data):
+            or not tags.RESIDENT.get(rcol.data, False) or not H.is_sorted(rcol.data):
         return None
     if j.residual is not None and any(c not in names or names[c] not in raw.columns
                                       for c in col_refs(j.residual) if c in names):
@@ -510,7 +510,7 @@ def _semi_by_index_marks(lb: Batch, lk, lvalid, rk, rvalid, kind: str, ctx) -> O
     ascending, coalesced stores, and each probe row reads its mark -- instead
     of probing a hash table of the small side with every one of the big
     side's rows (1.4 ms -> ~0.2 ms at SF100). None when it does not apply."""
-    if rvalid is not None or not getattr(rk, "_igloo_resident", False) or rk.numel() < SEMI_MARKS_MIN_ROWS \
+    if rvalid is not None or not tags.RESIDENT.get(rk, False) or rk.numel() < SEMI_MARKS_MIN_ROWS \
             or rk.dtype not in (torch.int32, torch.int64) or lk.dtype not in (torch.int32, torch.int64) \
             or SEMI_MARKS_RATIO * lk.numel() > rk.numel():
         return None
@@ -782,7 +782,7 @@ def _in_place_semi(lb: Batch, rb: Batch, kind: str, on, residual, ctx) -> Option
             or 4 * lb.num_rows > n_src or rb.mask.numel() != n_src:
         return None
     col = rb.src.columns[k.cid]
-    if col.dtype.kind not in _INT_KEYS or col.valid is not None or not getattr(col.data, "_igloo_resident", False):
+    if col.dtype.kind not in _INT_KEYS or col.valid is not None or not tags.RESIDENT.get(col.data, False):
         return None
     full = Batch(dict(rb.src.columns.items()), n_src, rb.dist)
     cmp = _col_compare(residual, lb, full) if residual is not None else None
@@ -918,14 +918,11 @@ def concat_columns(cols: List[Column]) -> Column:
 # ====================================================================== multi join
 def _resident_ndv(t: torch.Tensor) -> int:
     """NDV of a resident key column (HyperLogLog, remembered on the tensor)."""
-    d = getattr(t, "_igloo_ndv", None)
+    d = tags.NDV.get(t)
     if d is None:
         with unlogged():      # remembered on the resident tensor: a one-time build
             d = max(1, int(round(H.hll_estimate(H.hll_sketch(t)))))
-        try:
-            t._igloo_ndv = d
-        except (AttributeError, RuntimeError):
-            pass
+        tags.NDV.set(t, d)
     return d
 
 
@@ -934,7 +931,7 @@ def _dense_lookup_ok(big: torch.Tensor, nq: int) -> bool:
     is built now, once): a lookup is two reads whatever the probe count, so
     the join needs no hash table even when the other side is not much
     smaller (TPC-H customer.c_custkey against 5.7M-22.7M filtered orders)."""
-    if not (DENSE_JOIN and getattr(big, "_igloo_resident", False) and nq >= H.DENSE_RESIDENT_MIN_QUERIES):
+    if not (DENSE_JOIN and tags.RESIDENT.get(big, False) and nq >= H.DENSE_RESIDENT_MIN_QUERIES):
         return False
     if not H.is_sorted(big):
         return False
@@ -1009,7 +1006,7 @@ def inner_pairs(lk, rk, lvalid, rvalid, ctx, identity_ok: bool = False):
                 lo, cnt = H.sorted_ranges(small, big, bvalid)
                 bidx, sidx = H.expand_ranges(lo, cnt, small.numel())
         return (sidx, bidx) if big_right else (bidx, sidx)
-    if dev.type == "cuda" and PERM_INDEX and bvalid is None and getattr(big, "_igloo_resident", False) \
+    if dev.type == "cuda" and PERM_INDEX and bvalid is None and tags.RESIDENT.get(big, False) \
             and big.numel() >= SORTED_JOIN_MIN_ROWS and PERM_INDEX_RATIO * small.numel() <= big.numel() \
             and small.numel() * (big.numel() / _resident_ndv(big)) * PERM_INDEX_SORT_FRAC <= big.numel():
         # unsorted resident column, much smaller other side: search its
@@ -1265,7 +1262,7 @@ def _in_place_side(side: "LateBatch", keys, other_rows: int, ctx):
     if not (isinstance(k, ColRef) and k.cid in bb.src.columns and not bb.has(k.cid)):
         return None
     col = bb.src.columns[k.cid]
-    if col.dtype.kind not in _INT_KEYS or col.valid is not None or not getattr(col.data, "_igloo_resident", False):
+    if col.dtype.kind not in _INT_KEYS or col.valid is not None or not tags.RESIDENT.get(col.data, False):
         return None
     if bb.num_rows < IN_PLACE_HASH_DENSITY * n_src and not H.is_sorted(col.data):
         return None
@@ -1744,8 +1741,8 @@ class MultiJoinExec(ExecNode):
                 if not ctx.spmd and b.num_rows:
                     c = ctx.evaluator.column(e, b)
                     # resident table columns: the sketch of the same tensor is reused across queries
-                    cached = getattr(c.data, "_igloo_ndv", None) if c.valid is None else None
-                base = getattr(c.data, "_igloo_base", None) if cached is None and not ctx.spmd and \
+                    cached = tags.NDV.get(c.data) if c.valid is None else None
+                base = tags.BASE.get(c.data) if cached is None and not ctx.spmd and \
                     b.num_rows and c.valid is None else None
                 if cached is not None:
                     g = cached
@@ -1761,7 +1758,7 @@ class MultiJoinExec(ExecNode):
                     if ctx.spmd:
                         # every rank takes part, even with an empty slice (collective order must match)
                         regs = ctx.comm.allreduce_max_tensor(regs)
-                    if b.num_rows and c.valid is None and getattr(c.data, "_igloo_resident", False):
+                    if b.num_rows and c.valid is None and tags.RESIDENT.get(c.data, False):
                         with unlogged():     # remembered on the resident column below
                             g = int(round(H.hll_estimate(regs)))
                     else:
@@ -1775,10 +1772,7 @@ class MultiJoinExec(ExecNode):
                     if ctx.spmd:
                         g = ctx.comm.allreduce_int(g)  # upper bound of the global NDV
                 if cached is None and not ctx.spmd and b.num_rows and c.valid is None and not c.is_dict:
-                    try:
-                        c.data._igloo_ndv = g
-                    except (AttributeError, RuntimeError):
-                        pass
+                    tags.NDV.set(c.data, g)
             rel["ndv"][key] = max(g, 1)
         return rel["ndv"][key]
 
@@ -1791,15 +1785,12 @@ def _derived_ndv(base, n: int) -> int:
     selected independently of the key) — no pass over the subset. D comes
     from one sketch of the source column, remembered on its tensor."""
     col, N = base
-    D = getattr(col.data, "_igloo_ndv", None)
+    D = tags.NDV.get(col.data)
     if D is None:
         k, _ = group_key_tensor(col)
         with unlogged():
             D = max(int(round(H.hll_estimate(H.hll_sketch(k)))) if k.is_cuda else H.ndv(k), 1)
-        try:
-            col.data._igloo_ndv = D
-        except (AttributeError, RuntimeError):
-            pass
+        tags.NDV.set(col.data, D)
     sel = min(n / max(N, 1), 1.0)
     return max(1, min(n, int(round(D * (1.0 - (1.0 - sel) ** (N / D))))))
 

@@ -22,7 +22,7 @@ from ..ops import misc as M
 from ..ops import strings as S
 from ..ops._lib import (check_not_capturing, device_ints, launch, ptr, stream, to_host_f64s, to_host_int,
                        to_host_ints, unlogged)
-from ..utils import trace as _trace
+from ..utils import tags, trace as _trace
 from ..ops.gather import gather_tensor, take, take_many
 from ..ops.select import MaskRows, compact_columns, exclusive_scan, mask_to_indices
 from ..sql import logical as L
@@ -48,10 +48,7 @@ COMPACT = True
 
 def _tag_base(col: Column, src: Column, n_src: int):
     if NDV_DERIVED and col.valid is None and not col.is_dict:
-        try:   # filtered subset of a source column: its NDV derives from the source's
-            col.data._igloo_base = (src, n_src)
-        except (AttributeError, RuntimeError):
-            pass
+        tags.BASE.set(col.data, (src, n_src))   # filtered subset of a source column: its NDV derives from the source's
 
 
 class ScanExec(ExecNode):

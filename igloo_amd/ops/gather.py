@@ -6,40 +6,15 @@ join/filter/sort. Negative indices produce NULL rows (outer-join padding).
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Sequence
 
 import torch
 
 from ..columnar import Column
+from ..utils.tags import inherit_take, origin  # noqa: F401  (origin: ops/hashing.py imports it from here)
 from ._lib import is_gpu, launch, ptr, stream, to_host_ints
 from .packed_gather import packed_take
 from .select import offsets_from_lengths
-
-
-def origin(t: torch.Tensor) -> Optional[torch.Tensor]:
-    """The resident table column every value of ``t`` was gathered from (no
-    negative rows), or None: ``t`` itself, a filtered scan's source
-    (exec/scan.py _tag_base) or the origin a gather inherited (take_many).
-    ops/hashing.py key_bound derives key ranges from it without a readback."""
-    if getattr(t, "_igloo_resident", False):
-        return t
-    o = getattr(t, "_igloo_origin", None)
-    if o is not None:
-        return o
-    base = getattr(t, "_igloo_base", None)
-    if base is not None and base[0].data.dtype == t.dtype:
-        return origin(base[0].data)
-    return None
-
-
-def _inherit(dst: torch.Tensor, src: torch.Tensor, idx: Optional[torch.Tensor] = None) -> None:
-    o = origin(src)
-    if o is not None:
-        dst._igloo_origin = o
-    if idx is not None and getattr(idx, "_igloo_incr", False) and getattr(src, "_igloo_sorted", False) is True:
-        # rows of a sorted column taken in row order stay sorted: later
-        # sorted-join / run-grouping checks need no pass (ops/hashing.py is_sorted)
-        dst._igloo_sorted = True
 
 
 def _cpu_take_tensor(t: torch.Tensor, idx: torch.Tensor, neg: bool) -> torch.Tensor:
@@ -161,9 +136,7 @@ def take_many(cols: Sequence[Column], idx: torch.Tensor, neg: bool = False) -> L
         valid = torch.empty(n, dtype=torch.bool, device=idx.device) if need_valid else None
         descs.append((_src_ptr(c.data), ptr(data), esz, _src_ptr(c.valid), ptr(valid), c.data.shape[0]))
         if not neg:
-            _inherit(data, c.data, idx)
-            if getattr(idx, "_igloo_incr", False) and getattr(c.data, "_igloo_distinct", False):
-                data._igloo_distinct = True
+            inherit_take(data, c.data, idx)
         out.append(Column(c.dtype, data, valid, dictionary=c.dictionary))
     if gpu and descs and n:
         N = launch("gather_multi")
@@ -184,7 +157,7 @@ def gather_tensor(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         esz = t.element_size() * (t.shape[1] if t.dim() == 2 else 1)
         launch("gather_multi").gather_multi(ptr(idx), idx.dtype == torch.int64, n,
                                             [(ptr(t), ptr(out), esz, 0, 0, t.shape[0])], stream(idx))
-    _inherit(out, t, idx)
+    inherit_take(out, t, idx, distinct=False)
     return out
 
 

@@ -16,6 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from ..utils import tags
 from .gather import origin as _origin
 from ._lib import capturing, check_not_capturing, is_gpu, launch, native, ptr, stream, to_host_f64s, to_host_int, to_host_ints, unlogged
 from .select import exclusive_scan, mask_to_indices
@@ -52,7 +53,7 @@ def column_stats(keys: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Tu
     csrc/kernels/util.hip and one host sync on the GPU. Remembered on resident
     key columns (no validity)."""
     if valid is None:
-        hit = getattr(keys, "_igloo_stats", None)
+        hit = tags.STATS.get(keys)
         if hit is not None:
             return hit
     n = keys.numel()
@@ -68,7 +69,7 @@ def column_stats(keys: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Tu
     N.column_stats(ptr(keys.contiguous()), keys.dtype == torch.int64,
                    ptr(valid.contiguous() if valid is not None else None), n, ptr(buf), stream(keys))
     out = buf[:3]
-    if valid is None and getattr(keys, "_igloo_resident", False):
+    if valid is None and tags.RESIDENT.get(keys, False):
         with unlogged():      # remembered below: a one-time build (ops/_lib.py unlogged)
             mn, mx, bad = to_host_ints(out)
     else:
@@ -78,12 +79,8 @@ def column_stats(keys: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Tu
         # remembered on any key tensor (like is_sorted's flag): a sortedness
         # check followed by a range lookup of the same keys (group_ids_ex ->
         # group_ids, inner_pairs -> JoinTable) reads the stats back once
-        try:
-            keys._igloo_stats = res
-            if getattr(keys, "_igloo_resident", False):
-                keys._igloo_sorted = res[1]
-        except (AttributeError, RuntimeError):
-            pass
+        if tags.STATS.set(keys, res) and tags.RESIDENT.get(keys, False):
+            tags.SORTED.set(keys, res[1])
     return res
 
 
@@ -118,13 +115,13 @@ def key_bound(keys: torch.Tensor) -> Optional[Tuple[int, int]]:
     dictionary codes lie in [0, dictionary size)). Looser than ``key_range``
     for a filtered subset; callers use it where a bound suffices
     (direct-mapped table spans, bit widths, overflow-free sums)."""
-    b = getattr(keys, "_igloo_bound", None)
+    b = tags.BOUND.get(keys)
     if b is not None:
         return _check_bound(keys, b)
     o = _origin(keys)
     if o is None or o.dtype != keys.dtype or o.dim() != 1:
         return None
-    st = getattr(o, "_igloo_stats", None)
+    st = tags.STATS.get(o)
     if st is None:
         if capturing():
             return None
@@ -153,16 +150,12 @@ def key_unique(keys: torch.Tensor) -> bool:
     that select rows in order, ops/gather.py take_many), distinct rows (a resident column, or a filtered scan's rows of one,
     in row order) of a resident column whose values are unique (checked once
     and remembered on it)."""
-    if getattr(keys, "_igloo_distinct", False):
+    if tags.DISTINCT.get(keys, False):
         return _check_unique(keys, "a distinct tag")
-    if getattr(keys, "_igloo_resident", False):
-        o = keys
-    else:
-        base = getattr(keys, "_igloo_base", None)
-        if base is None or base[0].data.dtype != keys.dtype or not getattr(base[0].data, "_igloo_resident", False):
-            return False
-        o = base[0].data
-    u = getattr(o, "_igloo_unique", None)
+    o = keys if tags.RESIDENT.get(keys, False) else tags.base_column(keys)
+    if o is None or not tags.RESIDENT.get(o, False):
+        return False
+    u = tags.UNIQUE.get(o)
     if u is None:
         if capturing() or not is_gpu(o) or o.dim() != 1:
             return False
@@ -179,9 +172,7 @@ def key_unique(keys: torch.Tensor) -> bool:
                 u = to_host_int((o[1:] == o[:-1]).any().to(torch.int64)) == 0
             else:
                 u = group_ids(o)[1] == n
-        try:
-            o._igloo_unique = u
-        except (AttributeError, RuntimeError):
+        if not tags.UNIQUE.set(o, u):
             return False
     return u and _check_unique(keys, "the resident base column's uniqueness" if o is not keys else
                                "a resident column's uniqueness")
@@ -373,7 +364,7 @@ class JoinTable:
             N.probe_write(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
                           self.kmin, self.direct, ptr(words), ptr(toff), ptr(pidx), it == torch.int64, ptr(bidx),
                           pidx.numel(), st)
-        pidx._igloo_incr = True      # hit rows in row order
+        tags.INCR.set(pidx, True)    # hit rows in row order
         return pidx, bidx
 
     def probe_pairs(self, pkeys: torch.Tensor, pvalid: Optional[torch.Tensor] = None,
@@ -464,26 +455,22 @@ SORTED_CHECK_ROWS = 1 << 20
 def is_sorted(keys: torch.Tensor) -> bool:
     """Non-decreasing check (one pass; remembered on the tensor object, so the
     resident key columns of a table are checked once)."""
-    hit = getattr(keys, "_igloo_sorted", None)
+    hit = tags.SORTED.get(keys)
     if hit is not None:
-        if hit and CHECK_KEY_TAGS and not capturing() and not getattr(keys, "_igloo_resident", False) \
+        if hit and CHECK_KEY_TAGS and not capturing() and not tags.RESIDENT.get(keys, False) \
                 and keys.numel() > 1 and keys.is_cuda:
             # test mode: a sortedness tag inferred through gathers must hold
             if to_host_int((keys[1:] < keys[:-1]).any().to(torch.int64)):
                 raise AssertionError("an inferred sorted tag does not hold")
         return hit
-    base = getattr(keys, "_igloo_base", None)
-    if base is not None and base[0].data.dtype == keys.dtype and is_sorted(base[0].data):
+    base = tags.base_column(keys)
+    if base is not None and is_sorted(base):
         # a filtered scan's rows of a sorted source column, in row order
         # (exec/scan.py _tag_base): sorted without another pass (the
         # source's flag is computed once and remembered on it)
         return True
-    n = keys.numel()
-    r = True if n < 2 else column_stats(keys)[1]
-    try:
-        keys._igloo_sorted = r
-    except (AttributeError, RuntimeError):
-        pass
+    r = keys.numel() < 2 or column_stats(keys)[1]
+    tags.SORTED.set(keys, r)
     return r
 
 
@@ -497,11 +484,11 @@ def dense_index(big: torch.Tensor, build: bool = True, queries: Optional[int] = 
     ``(kmin, kmax, first)`` with first[k - kmin] = first row whose key >= k,
     or None when the key span is too sparse. Remembered on the tensor object
     (resident table columns build it once)."""
-    hit = getattr(big, "_igloo_dense", None)
+    hit = tags.DENSE.get(big)
     # (the sorted keys of a resident column's secondary index live as long as
     # the column: their table is built once too -- Q9's 1.1M green parts
     # searched 600M l_partkey keys by bisection, 0.93 ms per query)
-    resident = getattr(big, "_igloo_resident", False) or getattr(big, "_igloo_index_keys", False)
+    resident = tags.RESIDENT.get(big, False) or tags.INDEX_KEYS.get(big, False)
     if hit or (hit is False and (queries is None or resident)):
         return hit or None
     if resident:
@@ -514,7 +501,7 @@ def dense_index(big: torch.Tensor, build: bool = True, queries: Optional[int] = 
             return _dense_index_build(big, None, resident=True)
     if not build:
         return None
-    rng = getattr(big, "_igloo_range", None)
+    rng = tags.RANGE.get(big)
     if hit is False and rng is not None and rng[1] - rng[0] + 1 > _dense_limit(big.numel(), queries):
         return None           # still too sparse for this many lookups: nothing to build
     return _dense_index_build(big, queries)    # an intermediate: built (and read back) every execution
@@ -540,13 +527,10 @@ def _dense_index_build(big: torch.Tensor, queries: Optional[int], resident: bool
     nb = big.numel()
     idx = False
     if nb:
-        rng = getattr(big, "_igloo_range", None)
+        rng = tags.RANGE.get(big)
         if rng is None:
             rng = tuple(to_host_ints(torch.stack([big[0].to(torch.int64), big[-1].to(torch.int64)])))
-            try:
-                big._igloo_range = rng
-            except (AttributeError, RuntimeError):
-                pass
+            tags.RANGE.set(big, rng)
         kmin, kmax = rng
         span = kmax - kmin + 1
         if span <= _dense_limit(nb, queries, resident):
@@ -565,10 +549,7 @@ def _dense_index_build(big: torch.Tensor, queries: Optional[int], resident: bool
                 N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
                                     it == torch.int64, 0, st)
             idx = (kmin, kmax, first)
-    try:
-        big._igloo_dense = idx
-    except (AttributeError, RuntimeError):
-        pass
+    tags.DENSE.set(big, idx)
     return idx or None
 
 
@@ -648,15 +629,13 @@ def search_fence(big: torch.Tensor) -> Optional[torch.Tensor]:
     bytes, kept with it like the other derived structures): binary searches
     first narrow to one 256-row window through it (L2/MALL-resident), then
     touch only that window of the column (csrc/kernels/ranges.hip)."""
-    if big.numel() < SEARCH_FENCE_MIN_ROWS or not getattr(big, "_igloo_resident", False):
+    if big.numel() < SEARCH_FENCE_MIN_ROWS or not tags.RESIDENT.get(big, False):
         return None
-    hit = getattr(big, "_igloo_fence", None)
+    hit = tags.FENCE.get(big)
     if hit is None:
         check_not_capturing("search fence of a resident column")
         hit = big[::native().SEARCH_FENCE].contiguous()
-        try:
-            big._igloo_fence = hit
-        except (AttributeError, RuntimeError):
+        if not tags.FENCE.set(big, hit):
             return None
     return hit
 
@@ -668,18 +647,14 @@ def perm_index(keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     structures (charged to the column in the HBM cache budget) —
     a join with a much smaller side then reads only the matching ranges
     instead of probing every row of the column."""
-    hit = getattr(keys, "_igloo_perm", None)
+    hit = tags.PERM.get(keys)
     if hit is not None:
         return hit
     from .sort import perm_sort_int
     with unlogged():
         out = perm_sort_int(keys)
-    try:
-        out[0]._igloo_sorted = True
-        out[0]._igloo_index_keys = True
-        keys._igloo_perm = out
-    except (AttributeError, RuntimeError):
-        pass
+    if tags.SORTED.set(out[0], True) and tags.INDEX_KEYS.set(out[0], True):
+        tags.PERM.set(keys, out)
     return out
 
 
@@ -818,10 +793,24 @@ def group_ids_ex(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor, b
             g = starts.numel()
             gid = torch.empty(n, dtype=torch.int32, device=keys.device)
             launch("fill_runs").fill_runs(ptr(starts), starts.dtype == torch.int64, g, n, ptr(gid), stream(keys))
-            gid._igloo_bound = (0, max(g - 1, 0))
+            tags.BOUND.set(gid, (0, max(g - 1, 0)))
             return gid, g, starts.to(torch.int32), True
     gid, g, rep = group_ids(keys)
     return gid, g, rep, False
+
+
+def _group_table(keys: torch.Tensor, n: int) -> Tuple[int, bool, int]:
+    """(kmin, direct-mapped?, slots) of the group-by table over ``keys``."""
+    bnd = key_bound(keys)
+    if bnd is not None and (bnd[1] - bnd[0] + 1 <= 2 * n + 65536 or n < BOUND_TRUST_ROWS):
+        kmin, kmax = bnd         # a readback-free bound decides: no range readback
+    elif tags.HASHED.get(keys, False) and n > 1:
+        kmin, kmax = 0, 2**62    # 64-bit hashes: the hash table, no range readback
+    else:
+        kmin, kmax = key_range(keys)
+    span = kmax - kmin + 1
+    direct = span <= 2 * n + 65536 and span < 2**31 - 1
+    return kmin, direct, span if direct else _next_pow2(2 * n)
 
 
 def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
@@ -839,16 +828,7 @@ def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
         g = uniq.numel()
         rep = torch.full((g,), n, dtype=torch.int64).scatter_reduce(0, inv, torch.arange(n), reduce="amin")
         return inv.to(torch.int32), g, rep.to(torch.int32)
-    bnd = key_bound(keys)
-    if bnd is not None and (bnd[1] - bnd[0] + 1 <= 2 * n + 65536 or n < BOUND_TRUST_ROWS):
-        kmin, kmax = bnd         # a readback-free bound decides: no range readback
-    elif getattr(keys, "_igloo_hashed", False) and n > 1:
-        kmin, kmax = 0, 2**62    # 64-bit hashes: the hash table, no range readback
-    else:
-        kmin, kmax = key_range(keys)
-    span = kmax - kmin + 1
-    direct = span <= 2 * n + 65536 and span < 2**31 - 1
-    cap = span if direct else _next_pow2(2 * n)
+    kmin, direct, cap = _group_table(keys, n)
     N = launch("groupby")
     s = stream(keys)
     k64 = keys.dtype == torch.int64
@@ -882,7 +862,7 @@ def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
         remap = newpos.index_select(0, first)
         gid = gather_tensor(remap, gid)
         rep = order.to(torch.int32)
-    gid._igloo_bound = (0, max(g - 1, 0))     # readback-free bound for packing / regrouping
+    tags.BOUND.set(gid, (0, max(g - 1, 0)))   # readback-free bound for packing / regrouping
     return gid, g, rep
 
 
@@ -900,16 +880,7 @@ def first_rows_mask(keys: torch.Tensor) -> torch.Tensor:
             _, _, rep = group_ids(keys)
             mark[rep.long()] = True
         return mark
-    bnd = key_bound(keys)
-    if bnd is not None and (bnd[1] - bnd[0] + 1 <= 2 * n + 65536 or n < BOUND_TRUST_ROWS):
-        kmin, kmax = bnd
-    elif getattr(keys, "_igloo_hashed", False) and n > 1:
-        kmin, kmax = 0, 2**62
-    else:
-        kmin, kmax = key_range(keys)
-    span = kmax - kmin + 1
-    direct = span <= 2 * n + 65536 and span < 2**31 - 1
-    cap = span if direct else _next_pow2(2 * n)
+    kmin, direct, cap = _group_table(keys, n)
     s = stream(keys)
     trow = torch.full((cap,), INT32_MAX, dtype=torch.int32, device=dev)
     tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
@@ -930,10 +901,10 @@ def hll_sketch(keys: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Opti
     Sketches of several ranks merge by element-wise max."""
     src = keys
     if valid is None:
-        hit = getattr(src, "_igloo_hll", None)
+        hit = tags.HLL.get(src)
         if hit is not None:   # resident table columns are sketched once (like is_sorted)
             return hit
-    if valid is None and getattr(src, "_igloo_resident", False):
+    if valid is None and tags.RESIDENT.get(src, False):
         check_not_capturing("sketch of a resident column")   # kept on the column: a one-time build
     keys = _keys_ok(keys)
     n = keys.numel()
@@ -946,10 +917,7 @@ def hll_sketch(keys: torch.Tensor, valid: Optional[torch.Tensor] = None) -> Opti
     ws = torch.empty(N.hll_blocks(n) * HLL_M, dtype=torch.uint8, device=keys.device)
     N.hll_sketch(ptr(keys), keys.dtype == torch.int64, ptr(valid), n, ptr(ws), ptr(regs), stream(keys))
     if valid is None:
-        try:
-            src._igloo_hll = regs
-        except (AttributeError, RuntimeError):
-            pass
+        tags.HLL.set(src, regs)
     return regs
 
 
@@ -1046,7 +1014,7 @@ def key_ranges(cols: Sequence[torch.Tensor]) -> List[Tuple[int, int]]:
         if c.numel() == 0:
             out[i] = (0, 0)
             continue
-        hit = getattr(c, "_igloo_stats", None)
+        hit = tags.STATS.get(c)
         if hit is not None and hit[0] is not None:
             out[i] = hit[0]
         elif is_gpu(c) and c.dtype in (torch.int32, torch.int64) and c.dim() == 1:

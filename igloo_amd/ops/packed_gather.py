@@ -29,6 +29,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from ..columnar import Column
+from ..utils import tags
 from . import _lib
 from ._lib import launch, ptr, stream
 
@@ -59,14 +60,14 @@ def _eligible(c: Column, rows: int) -> bool:
     d = c.data
     return (not c.is_plain_string and not c.dtype.is_nested and d.dim() == 1 and d.dtype in _FIXED and d.is_cuda
             and len(d) == rows
-            and getattr(d, "_igloo_resident", False) and (c.valid is None or c.valid.numel() == rows))
+            and tags.RESIDENT.get(d, False) and (c.valid is None or c.valid.numel() == rows))
 
 
 def _find(cands: Sequence[Column], want: List[Member]) -> Optional[Pack]:
     """The kept copy holding the most of ``want`` (at least two), or None."""
     best, hit = None, 1
     for c in cands:
-        for pk in getattr(c.data, "_igloo_packed", None) or ():
+        for pk in tags.PACKED.get(c.data) or ():
             k = sum(m in pk[1] for m in want)
             if k > hit:
                 best, hit = pk, k
@@ -105,9 +106,7 @@ def _build(cols: Sequence[Column]) -> Optional[Pack]:
         members[_member(c)] = (offs[vi], v.element_size(), _FIXED[v.dtype], offs[vv] if vv >= 0 else -1)
     pk: Pack = (packed, members, rb)
     owner = cols[0].data
-    try:
-        owner._igloo_packed = list(getattr(owner, "_igloo_packed", None) or ()) + [pk]
-    except (AttributeError, RuntimeError):
+    if not tags.PACKED.set(owner, list(tags.PACKED.get(owner) or ()) + [pk]):
         return None
     _live.add(packed)
     STATS["builds"] += 1
@@ -140,7 +139,7 @@ def packed_take(cols: Sequence[Column], idx: torch.Tensor, neg: bool) -> Dict[in
     pos = [i for i, c in enumerate(cols) if rows > 0 and _eligible(c, rows)]
     if len(pos) < 2:
         return {}
-    if getattr(idx, "_igloo_incr", False) and n > MAX_ASC_DENSITY * rows:
+    if tags.INCR.get(idx, False) and n > MAX_ASC_DENSITY * rows:
         return {}
     cand = [cols[i] for i in pos]
     want = [_member(c) for c in cand]
@@ -170,10 +169,7 @@ def packed_take(cols: Sequence[Column], idx: torch.Tensor, neg: bool) -> Dict[in
             valid = torch.empty(n, dtype=torch.bool, device=idx.device)
             fields.append((ptr(valid), 0, 1, 1, 2))
         if not neg:
-            from .gather import _inherit
-            _inherit(data, c.data, idx)
-            if getattr(idx, "_igloo_incr", False) and getattr(c.data, "_igloo_distinct", False):
-                data._igloo_distinct = True
+            tags.inherit_take(data, c.data, idx)
         out[i] = Column(c.dtype, data, valid, dictionary=c.dictionary)
     if len(out) < 2:
         return {}

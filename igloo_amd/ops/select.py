@@ -5,6 +5,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
+from ..utils import tags
 from ._lib import idx_dtype, is_gpu, launch, ptr, stream, to_host_int, to_host_ints
 
 
@@ -22,16 +23,16 @@ def attach_tile_counts(mask: torch.Tensor, tc: torch.Tensor) -> None:
     written with it (exec/fused_jit.py tiled mask kernel): the next count of
     this mask scans them instead of re-reading the mask. Tied to the mask's
     version counter, so an in-place change of the mask drops them."""
-    mask._igloo_tc = (tc, mask._version)
+    tags.TC.set(mask, (tc, mask._version))
 
 
 def _select_count(N, mask: torch.Tensor, n: int, tiles: int, s) -> torch.Tensor:
     """ws [tiles + 1] int64: exclusive per-tile offsets of the set rows of
     ``mask`` and their total (select.hip select_count) -- from the tile counts
     the mask's kernel wrote when it has them (consumed: scanned in place)."""
-    pre = getattr(mask, "_igloo_tc", None)
+    pre = tags.TC.get(mask)
     if pre is not None:
-        mask._igloo_tc = None
+        tags.TC.set(mask, None)
         ws, ver = pre
         if ver == mask._version and ws.numel() == tiles + 1 and tiles > _SMALL_TILES:
             N.select_scan_counts(ptr(ws), tiles, ptr(ws) + 8 * tiles, s)
@@ -49,7 +50,7 @@ def mask_to_indices(mask: torch.Tensor, total: Optional[int] = None) -> torch.Te
     it = idx_dtype(n)
     if not is_gpu(mask):
         out = torch.nonzero(mask).flatten().to(it)
-        out._igloo_incr = True
+        tags.INCR.set(out, True)
         return out
     mask = mask.contiguous()
     N = launch("select")
@@ -61,7 +62,7 @@ def mask_to_indices(mask: torch.Tensor, total: Optional[int] = None) -> torch.Te
     out = torch.empty(total, dtype=it, device=mask.device)
     if total:
         N.select_write(ptr(mask), n, ptr(ws), ptr(out), it == torch.int64, total, s)
-    out._igloo_incr = True       # strictly increasing: gathers by it keep distinct rows distinct
+    tags.INCR.set(out, True)       # strictly increasing: gathers by it keep distinct rows distinct
     return out
 
 
@@ -116,7 +117,7 @@ class MaskRows:
             if self.total:
                 launch("select").select_write(ptr(self.mask), n, ptr(self._ws), ptr(out), out.dtype == torch.int64,
                                               self.total, stream(self.mask))
-            out._igloo_incr = True
+            tags.INCR.set(out, True)
             self._idx, self._ws = out, None
         return self._idx
 
@@ -187,7 +188,7 @@ def compact_columns(mask: torch.Tensor, cols, total: Optional[int] = None, want_
     copied through them, with no index vector between the mask and the
     gathers. Plain string columns go through the indices."""
     from ..columnar import Column
-    from .gather import _inherit, take_many
+    from .gather import take_many
     assert mask.dtype == torch.bool and mask.dim() == 1
     n = mask.numel()
     if not is_gpu(mask):
@@ -213,9 +214,7 @@ def compact_columns(mask: torch.Tensor, cols, total: Optional[int] = None, want_
         esz = d.element_size() * (d.shape[1] if d.dim() == 2 else 1)
         dv = torch.empty(total, dtype=torch.bool, device=mask.device) if c.valid is not None else None
         descs.append((ptr(d), ptr(out), esz, ptr(c.valid.contiguous() if c.valid is not None else None), ptr(dv)))
-        _inherit(out, c.data)
-        if getattr(c.data, "_igloo_distinct", False):
-            out._igloo_distinct = True        # rows kept in order: still distinct
+        tags.inherit_take(out, c.data, True, sorted=False)    # rows kept in order: still distinct
         outs[k] = Column(c.dtype, out, dv, dictionary=c.dictionary)
     if n and (descs or idx is not None):
         first = True
@@ -224,7 +223,7 @@ def compact_columns(mask: torch.Tensor, cols, total: Optional[int] = None, want_
                              ptr(idx) if first and idx is not None else 0, it == torch.int64, total, s)
             first = False
     if idx is not None:
-        idx._igloo_incr = True
+        tags.INCR.set(idx, True)
     if plain:
         for k, c in zip([k for k, c in enumerate(cols) if c.is_plain_string], take_many(plain, idx)):
             outs[k] = c

@@ -20,6 +20,7 @@ import torch
 
 from .. import types as T
 from ..columnar import Column
+from ..utils import tags
 from .gather import gather_tensor
 from ._lib import capture_hold, capturing, check_not_capturing, device_ints, is_gpu, launch, note_host_step, ptr, stream, to_host_int
 from .gather import take
@@ -529,7 +530,7 @@ def hash64(col: Column) -> torch.Tensor:
                             dtype=torch.int64)
     out = torch.empty(n, dtype=torch.int64, device=col.device)
     launch("str_hash64").str_hash64(ptr(col.offsets), ptr(col.data), n, ptr(col.valid), ptr(out), stream(out))
-    out._igloo_hashed = True     # spread over 64 bits: group_ids goes straight to its hash table
+    tags.HASHED.set(out, True)   # spread over 64 bits: group_ids goes straight to its hash table
     return out
 
 

@@ -40,6 +40,7 @@ from ..ops.gather import take_many
 from ..ops._lib import device_ints, to_host_ints
 from ..sql import logical as L
 from ..sql.expr import AggCall, ColRef, Expr
+from ..utils import tags
 from ..utils.errors import NotSupported
 from ..utils.log import get_logger
 
@@ -896,7 +897,7 @@ def _semi_by_range_marks(lb: Batch, rb: Batch, join: L.Join, ctx) -> Optional[Ba
             # one pass over the keys (ops/_lib: the mark_keys kernel), no temporaries
             from ..ops._lib import launch, ptr, stream
             rk = rcol.data if rcol.data.dtype in (torch.int32, torch.int64) else rcol.data.to(torch.int64)
-            if rcol.valid is None and getattr(rk, "_igloo_resident", False) and rk.numel() >= (1 << 20):
+            if rcol.valid is None and tags.RESIDENT.get(rk, False) and rk.numel() >= (1 << 20):
                 # a resident key column: its sorted secondary index (built once,
                 # kept with the column) makes the mark stores ascending --
                 # coalesced, instead of one random byte store per row (Q22:

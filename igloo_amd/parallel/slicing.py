@@ -40,6 +40,7 @@ import torch
 from ..columnar import Column
 from ..sql import logical as L
 from ..sql.expr import Expr, SubqueryExpr
+from ..utils import tags
 
 
 def range_tag(world: int, kmin: int, chunk: int) -> tuple:
@@ -233,13 +234,10 @@ def slice_columns(cols: Dict[str, Column], n: int, key: str, world: int, rank: i
     from ..ops._lib import device_ints, to_host_ints, unlogged
     kc = cols.get(key)
     kt = kc.data if kc is not None else None
-    memo = getattr(kt, "_igloo_slices", None) if kt is not None else None
+    memo = tags.SLICES.get(kt)      # (no key column: kt is None, nothing is remembered)
     if memo is None:
         memo = {}
-        try:
-            kt._igloo_slices = memo
-        except (AttributeError, RuntimeError):
-            pass
+        tags.SLICES.set(kt, memo)
     plan = memo.get(("bounds", world, rank))
     if plan is None:
         with unlogged():    # remembered on the resident key tensor: a one-time cost

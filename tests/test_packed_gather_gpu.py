@@ -51,10 +51,13 @@ def test_packed_take_matches_columns(gpu_device, monkeypatch, neg, incr, i64):
     it = torch.from_numpy(idx.astype(np.int64 if i64 else np.int32)).to(DEV)
     if incr:
         it._igloo_incr = True
+    cols[1].data._igloo_distinct = True      # a declared fact: only its propagation is checked
     before = PG.STATS["gathers"]
     got = take_many(cols, it, neg=neg)
     torch.cuda.synchronize()
     assert PG.STATS["gathers"] == before + 1
+    # rows taken in increasing order keep a distinct-tagged member distinct; nothing else is tagged
+    assert [getattr(c.data, "_igloo_distinct", False) for c in got] == [False, incr, False, False, False]
     # int8 + int32 + int64 + float32 + int32/validity: all fit one 32-byte row
     assert all(getattr(c.data, "_igloo_packed", None) is None for c in cols[1:]) and cols[0].data._igloo_packed
     ii = torch.from_numpy(idx).long()
