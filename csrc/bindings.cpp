@@ -92,6 +92,7 @@ py::dict leaf_dict(const io::PqLeaf& l) {
   d["max_rep"] = l.max_rep;
   d["converted_type"] = l.converted_type;
   d["logical"] = l.logical;
+  d["tz"] = l.tz;
   d["scale"] = l.scale;
   d["precision"] = l.precision;
   return d;
@@ -604,16 +605,20 @@ PYBIND11_MODULE(_native, m) {
                        P<uint8_t>(out), S(s));
   });
 
-  m.def("strfmt_lengths", [](const std::string& fmt, bool is_date, uintptr_t v, int64_t n, uintptr_t len,
-                             uintptr_t s) {
-    kern::strfmt_lengths(reinterpret_cast<const uint8_t*>(fmt.data()), (int)fmt.size(), is_date, P<const void>(v), n,
-                         P<int64_t>(len), S(s));
+  m.def("strfmt_lengths", [](const std::string& fmt, bool is_date, uintptr_t v, uintptr_t offs, int64_t n,
+                             uintptr_t len, uintptr_t s) {
+    kern::strfmt_lengths(reinterpret_cast<const uint8_t*>(fmt.data()), (int)fmt.size(), is_date, P<const void>(v),
+                         P<const int32_t>(offs), n, P<int64_t>(len), S(s));
   });
-  m.def("strfmt_write", [](const std::string& fmt, bool is_date, uintptr_t v, int64_t n, uintptr_t off,
-                           int64_t out_cap, uintptr_t out, uintptr_t s) {
-    kern::strfmt_write(reinterpret_cast<const uint8_t*>(fmt.data()), (int)fmt.size(), is_date, P<const void>(v), n,
-                       P<const int64_t>(off), out_cap, P<uint8_t>(out), S(s));
+  m.def("strfmt_write", [](const std::string& fmt, bool is_date, uintptr_t v, uintptr_t offs, int64_t n,
+                           uintptr_t off, int64_t out_cap, uintptr_t out, uintptr_t s) {
+    kern::strfmt_write(reinterpret_cast<const uint8_t*>(fmt.data()), (int)fmt.size(), is_date, P<const void>(v),
+                       P<const int32_t>(offs), n, P<const int64_t>(off), out_cap, P<uint8_t>(out), S(s));
   });
+  m.def("tz_to_local", raw<&kern::tz_to_local>);
+  m.def("tz_to_utc", raw<&kern::tz_to_utc>);
+  m.def("tz_trunc", raw<&kern::tz_trunc>);
+  m.def("tz_part", raw<&kern::tz_part>);
   m.def("regex_lds_bytes", &kern::regex_lds_bytes);
   m.def("regex_dfa_match", raw<&kern::regex_dfa_match>);
   // span automaton as (table, cls, flags, nstates, nclasses, anchored_start, anchored_end)

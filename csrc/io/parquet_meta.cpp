@@ -154,6 +154,7 @@ class TReader {
 struct SchemaEl {
   int type = -1, type_length = 0, repetition = 0, num_children = 0, converted = -1, scale = 0, precision = 0;
   std::string name, logical;
+  bool utc = false;        // TIMESTAMP logical type with isAdjustedToUTC
   int lscale = -1, lprecision = -1;
 };
 
@@ -192,7 +193,8 @@ void parse_logical(TReader& r, SchemaEl& e) {
       case 8: {
         std::string unit = "us";
         r.each([&](int16_t f, int ft) {
-          if (f == 2) unit = time_unit(r);
+          if (f == 1) e.utc = r.boolean(ft);
+          else if (f == 2) unit = time_unit(r);
           else r.skip(ft);
         });
         e.logical = "timestamp_" + unit;
@@ -345,6 +347,7 @@ size_t flatten(const std::vector<SchemaEl>& s, size_t i, int def, int rep, const
   l.max_rep = rr;
   l.converted_type = e.converted;
   l.logical = e.logical.empty() ? logical_from_converted(e.converted) : e.logical;
+  l.tz = e.utc ? "UTC" : "";
   l.scale = e.lscale >= 0 ? e.lscale : e.scale;
   l.precision = e.lprecision >= 0 ? e.lprecision : e.precision;
   out.push_back(std::move(l));

@@ -48,6 +48,7 @@ struct PqLeaf {
   int converted_type = -1;
   int scale = 0, precision = 0;
   std::string logical;     // "", "string", "decimal", "date", "timestamp_ms/us/ns", "int8/16/32/64", "uint..."
+  std::string tz;          // "UTC": TIMESTAMP(isAdjustedToUTC = true), instants; "": local (naive) time
 };
 
 struct PqChunk {

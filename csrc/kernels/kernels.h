@@ -422,11 +422,27 @@ void digest_hex(int algo, const int64_t* off, const uint8_t* chars, int64_t n, u
 void uuid_v4(uint64_t seed, int64_t n, uint8_t* out, hipStream_t s);   // out: n * 36 bytes
 
 // ---- strfmt.hip (to_char / date_format with chrono-style patterns) --------------
-// v: int32 days (is_date) or int64 microseconds; lengths pass, then writes at off (bounded by out_cap)
-void strfmt_lengths(const uint8_t* fmt, int flen, bool is_date, const void* v, int64_t n, int64_t* len,
-                    hipStream_t s);
-void strfmt_write(const uint8_t* fmt, int flen, bool is_date, const void* v, int64_t n, const int64_t* off,
-                  int64_t out_cap, uint8_t* out, hipStream_t s);
+// v: int32 days (is_date) or int64 microseconds; lengths pass, then writes at off (bounded by out_cap).
+// offs: null, or each row's UTC offset in seconds for %z / %:z (v then holds local wall time)
+void strfmt_lengths(const uint8_t* fmt, int flen, bool is_date, const void* v, const int32_t* offs, int64_t n,
+                    int64_t* len, hipStream_t s);
+void strfmt_write(const uint8_t* fmt, int flen, bool is_date, const void* v, const int32_t* offs, int64_t n,
+                  const int64_t* off, int64_t out_cap, uint8_t* out, hipStream_t s);
+
+// ---- tz.hip (TIMESTAMP WITH TIME ZONE: conversions through a compiled zone table) ---
+// tab: one device buffer [trans P int64][wall P int64][offs P int32], P = 1 << log2p (utils/tzdb.py);
+// log2p < 0: a fixed-offset zone (fixed_off seconds, tab unused). utc_lo / wall_lo: where the 400-year
+// fold-back starts. Values are int64 microseconds; NULL rows may hold any bits.
+void tz_to_local(const int64_t* in, int64_t n, const int64_t* tab, int log2p, int fixed_off, int64_t utc_lo,
+                 int64_t wall_lo, int64_t* out, int32_t* off_out, hipStream_t s);   // off_out: seconds per row, or null
+void tz_to_utc(const int64_t* in, int64_t n, const int64_t* tab, int log2p, int fixed_off, int64_t utc_lo,
+               int64_t wall_lo, int64_t* out, hipStream_t s);
+// unit: 0 second 1 minute 2 hour 3 day 4 week 5 month 6 quarter 7 year (truncated in local time, result in UTC)
+void tz_trunc(const int64_t* in, int64_t n, const int64_t* tab, int log2p, int fixed_off, int64_t utc_lo,
+              int64_t wall_lo, int unit, int64_t* out, hipStream_t s);
+// field: 0 year 1 month 2 day 3 quarter 4 dow 5 doy 6 hour 7 minute 8 second 9 millisecond 10 microsecond 11 week
+void tz_part(const int64_t* in, int64_t n, const int64_t* tab, int log2p, int fixed_off, int64_t utc_lo,
+             int64_t wall_lo, int field, int32_t* out, hipStream_t s);
 
 // ---- regex.hip (byte-class DFA match per string; table built by ops/regex_dfa.py) ---
 size_t regex_lds_bytes(int nstates, int nclasses);

@@ -7,6 +7,10 @@
 // scan -> offsets on the host side), strfmt_write_kernel writes the bytes.
 // Supported: %Y %C %y %m %d %e %j %H %k %I %l %M %S %p %P %f %.3f %.6f %.9f
 // %a %A %b %h %B %u %w %F %T %D %R %s %% ; other characters are copied.
+// With a per-row UTC offset array (zoned timestamps: the values are already
+// local wall time, ops/timezone.py) also %z (+HHMM) and %:z (+HH:MM), rounded
+// to the minute like chrono; %#f (internal, CAST(timestamptz AS VARCHAR)) prints
+// .ffffff only when the microseconds are not zero.
 #include "common.h"
 #include "kernels.h"
 
@@ -16,6 +20,7 @@ namespace kern {
 namespace {
 
 constexpr int kMaxFmt = 128;
+constexpr int kNoOffset = INT32_MIN;
 
 struct Civil {
   int64_t y;
@@ -23,6 +28,7 @@ struct Civil {
   int hh, mi, ss;
   int64_t us;                // microseconds within the second
   int64_t epoch_s;
+  int off = kNoOffset;       // UTC offset in seconds (%z), zoned values only
 };
 
 __device__ inline Civil civil(int64_t t_us) {
@@ -86,6 +92,14 @@ struct Out {
   }
 };
 
+__device__ void offset(int off, bool colon, Out& o) {
+  o.ch(off < 0 ? '-' : '+');
+  const int mins = ((off < 0 ? -off : off) + 30) / 60;
+  o.num(mins / 60, 2);
+  if (colon) o.ch(':');
+  o.num(mins % 60, 2);
+}
+
 __device__ void format_one(const uint8_t* fmt, int flen, const Civil& c, Out& o) {
   for (int i = 0; i < flen; ++i) {
     const uint8_t f = fmt[i];
@@ -94,6 +108,16 @@ __device__ void format_one(const uint8_t* fmt, int flen, const Civil& c, Out& o)
       continue;
     }
     uint8_t s = fmt[++i];
+    if (c.off != kNoOffset && (s == ':' || s == '#') && i + 1 < flen && fmt[i + 1] == (s == ':' ? 'z' : 'f')) {
+      ++i;
+      if (s == ':') {
+        offset(c.off, true, o);
+      } else if (c.us) {
+        o.ch('.');
+        o.num(c.us, 6);
+      }
+      continue;
+    }
     int frac = 0;
     if (s == '.' && i + 1 < flen) {   // %.3f / %.6f / %.9f / %.f
       uint8_t dgt = fmt[i + 1];
@@ -143,8 +167,14 @@ __device__ void format_one(const uint8_t* fmt, int flen, const Civil& c, Out& o)
       case 'T': o.num(c.hh, 2); o.ch(':'); o.num(c.mi, 2); o.ch(':'); o.num(c.ss, 2); break;
       case 'R': o.num(c.hh, 2); o.ch(':'); o.num(c.mi, 2); break;
       case 'D': o.num(c.m, 2); o.ch('/'); o.num(c.d, 2); o.ch('/'); o.num(((c.y % 100) + 100) % 100, 2); break;
-      case 's': o.num(c.epoch_s, 1); break;
+      case 's': o.num(c.epoch_s - (c.off == kNoOffset ? 0 : c.off), 1); break;
       case '%': o.ch('%'); break;
+      case 'z':
+        if (c.off != kNoOffset) {
+          offset(c.off, false, o);
+          break;
+        }
+        [[fallthrough]];      // a naive value has no offset: %z is copied like any unknown spec
       default: o.ch('%'); o.ch(s); break;
     }
   }
@@ -156,24 +186,28 @@ struct FmtArgs {
   int is_date;     // values are int32 days (else int64 microseconds)
 };
 
-__device__ inline int64_t value_us(const FmtArgs& a, const void* v, int64_t r) {
-  return a.is_date ? (int64_t)((const int32_t*)v)[r] * 86400000000LL : ((const int64_t*)v)[r];
+__device__ inline Civil value_civil(const FmtArgs& a, const void* v, const int32_t* offs, int64_t r) {
+  Civil c = civil(a.is_date ? (int64_t)((const int32_t*)v)[r] * 86400000000LL : ((const int64_t*)v)[r]);
+  if (offs) c.off = offs[r];
+  return c;
 }
 
-__global__ __launch_bounds__(kBlock) void strfmt_len_kernel(FmtArgs a, const void* __restrict__ v, int64_t n,
+__global__ __launch_bounds__(kBlock) void strfmt_len_kernel(FmtArgs a, const void* __restrict__ v,
+                                                          const int32_t* __restrict__ offs, int64_t n,
                                                           int64_t* __restrict__ len) {
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
     Out o{nullptr};
-    format_one(a.fmt, a.flen, civil(value_us(a, v, r)), o);
+    format_one(a.fmt, a.flen, value_civil(a, v, offs, r), o);
     len[r] = o.n;
   }
 }
 
-__global__ __launch_bounds__(kBlock) void strfmt_write_kernel(FmtArgs a, const void* __restrict__ v, int64_t n,
+__global__ __launch_bounds__(kBlock) void strfmt_write_kernel(FmtArgs a, const void* __restrict__ v,
+                                                            const int32_t* __restrict__ offs, int64_t n,
                                                             const int64_t* __restrict__ off, int64_t out_cap,
                                                             uint8_t* __restrict__ out) {
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-    const Civil c = civil(value_us(a, v, r));
+    const Civil c = value_civil(a, v, offs, r);
     Out probe{nullptr};
     format_one(a.fmt, a.flen, c, probe);
     const int64_t o0 = off[r];
@@ -185,28 +219,29 @@ __global__ __launch_bounds__(kBlock) void strfmt_write_kernel(FmtArgs a, const v
 
 }  // namespace
 
-void strfmt_lengths(const uint8_t* fmt, int flen, bool is_date, const void* v, int64_t n, int64_t* len,
-                    hipStream_t s) {
+void strfmt_lengths(const uint8_t* fmt, int flen, bool is_date, const void* v, const int32_t* offs, int64_t n,
+                    int64_t* len, hipStream_t s) {
   if (flen > kMaxFmt) throw std::runtime_error("to_char: format longer than 128 bytes");
   if (n == 0) return;
   FmtArgs a;
   for (int i = 0; i < flen; ++i) a.fmt[i] = fmt[i];
   a.flen = flen;
   a.is_date = is_date;
-  hipLaunchKernelGGL(strfmt_len_kernel, dim3(grid_for(n, kBlock, 1 << 14)), dim3(kBlock), 0, s, a, v, n, len);
+  hipLaunchKernelGGL(strfmt_len_kernel, dim3(grid_for(n, kBlock, 1 << 14)), dim3(kBlock), 0, s, a, v, offs, n,
+                     len);
   check_launch("strfmt_len", s);
 }
 
-void strfmt_write(const uint8_t* fmt, int flen, bool is_date, const void* v, int64_t n, const int64_t* off,
-                  int64_t out_cap, uint8_t* out, hipStream_t s) {
+void strfmt_write(const uint8_t* fmt, int flen, bool is_date, const void* v, const int32_t* offs, int64_t n,
+                  const int64_t* off, int64_t out_cap, uint8_t* out, hipStream_t s) {
   if (flen > kMaxFmt) throw std::runtime_error("to_char: format longer than 128 bytes");
   if (n == 0) return;
   FmtArgs a;
   for (int i = 0; i < flen; ++i) a.fmt[i] = fmt[i];
   a.flen = flen;
   a.is_date = is_date;
-  hipLaunchKernelGGL(strfmt_write_kernel, dim3(grid_for(n, kBlock, 1 << 14)), dim3(kBlock), 0, s, a, v, n, off,
-                     out_cap, out);
+  hipLaunchKernelGGL(strfmt_write_kernel, dim3(grid_for(n, kBlock, 1 << 14)), dim3(kBlock), 0, s, a, v, offs, n,
+                     off, out_cap, out);
   check_launch("strfmt_write", s);
 }
 

@@ -250,10 +250,16 @@ class Parser {
       n->kids.push_back(statement());
     } else if (acceptKw("SET")) {
       n = make("set");
-      std::string name = ident();
-      while (acceptOp(".")) name += "." + ident();
-      n->str = name;
-      if (!acceptOp("=")) expectWord("to");
+      if (isWord("time") && isWord("zone", 1)) {  // SET TIME ZONE 'zone'
+        p_ += 2;
+        n->str = "time_zone";
+        if (!acceptOp("=")) acceptWord("to");
+      } else {
+        std::string name = ident();
+        while (acceptOp(".")) name += "." + ident();
+        n->str = name;
+        if (!acceptOp("=")) expectWord("to");
+      }
       n->kids.push_back(expr());
     } else if (acceptKw("SHOW")) {
       n = make("show");
@@ -261,6 +267,7 @@ class Parser {
         n->str = "all";
       } else {
         n->str = ident();
+        if (n->str == "time" && acceptWord("zone")) n->str = "time_zone";
         if (n->str == "columns" || n->str == "fields") {
           if (!acceptKw("FROM")) expectKw("IN");
           std::string t = ident();
@@ -441,6 +448,10 @@ class Parser {
     else
       t = upper(ident());
     if (t == "DOUBLE") acceptWord("precision");
+    if (t == "TIMESTAMP" && (isKw("WITH") || isWord("without")) && isWord("time", 1) && isWord("zone", 2)) {
+      t = isKw("WITH") ? "TIMESTAMP WITH TIME ZONE" : "TIMESTAMP WITHOUT TIME ZONE";
+      p_ += 3;
+    }
     if (t == "CHARACTER" && acceptWord("varying")) t = "VARCHAR";
     if (acceptOp("(")) {
       t += "(";
@@ -988,6 +999,12 @@ class Parser {
         c->kids.push_back(x);
         c->flags["type"] = typeName();
         x = c;
+      } else if (isWord("at") && isWord("time", 1) && isWord("zone", 2)) {  // x AT TIME ZONE 'zone'
+        p_ += 3;
+        auto f = make("func", "at_time_zone");
+        f->pos = x->pos;
+        f->kids = {x, primary()};
+        x = f;
       } else if (acceptOp("[")) {  // list element (1-based), struct field by name, or slice l[a:b]
         auto f = make("func", "array_element");
         f->pos = x->pos;

@@ -232,7 +232,9 @@ class Column:
             arr = arr.cast(pa.date32())
             np_vals = arr.cast(pa.int32()).fill_null(0).to_numpy(zero_copy_only=False)
         elif dtype.kind == "timestamp":
-            np_vals = arr.cast(pa.timestamp("us")).cast(pa.int64()).fill_null(0).to_numpy(zero_copy_only=False)
+            # a zoned array keeps its UTC instants: only the unit changes
+            src_tz = arr.type.tz if pa.types.is_timestamp(arr.type) else None
+            np_vals = arr.cast(pa.timestamp("us", tz=src_tz)).cast(pa.int64()).fill_null(0).to_numpy(zero_copy_only=False)
         elif dtype.kind == "bool":
             np_vals = arr.fill_null(False).to_numpy(zero_copy_only=False).astype(np.bool_)
         else:
@@ -289,7 +291,7 @@ class Column:
         if dt.kind == "date32":
             return pa.Array.from_buffers(pa.date32(), n, [validity, pa.py_buffer(x.astype(np.int32).tobytes())])
         if dt.kind == "timestamp":
-            return pa.Array.from_buffers(pa.timestamp("us"), n, [validity, pa.py_buffer(x.astype(np.int64).tobytes())])
+            return pa.Array.from_buffers(dt.to_arrow(), n, [validity, pa.py_buffer(x.astype(np.int64).tobytes())])
         if dt.kind == "bool":
             mask = None if self.valid is None else ~self.valid.cpu().numpy()
             return pa.array(x.astype(np.bool_), pa.bool_(), mask=mask)

@@ -115,6 +115,8 @@ def conversion(leaf: dict, dt: T.DataType) -> Optional[Tuple[str, int, int]]:
     if k == "timestamp":
         if phys != PHYS["INT64"]:
             return None
+        if dt.is_zoned and logical.startswith("timestamp") and leaf.get("tz") != "UTC":
+            return None        # zoned by the schema, local time in the file: the values are no instants
         unit = logical.rsplit("_", 1)[-1] if logical.startswith("timestamp") else "us"
         return {"ms": ("mul", 8, 1000), "us": ("copy", 8, 1), "ns": ("div", 8, 1000)}.get(unit)
     if k == "decimal":

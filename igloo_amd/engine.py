@@ -407,7 +407,13 @@ class QueryEngine:
         if k == "set":
             from .sql.binder import Binder as _B
             v = Binder(self.catalog, self._ids).bind_expr(st["c"][0], __import__("igloo_amd.sql.binder", fromlist=["Scope"]).Scope([]))
-            self.session[st["s"]] = getattr(v, "value", None)
+            name, val = st["s"], getattr(v, "value", None)
+            if name.lower() in ("time_zone", "timezone", "datafusion.execution.time_zone"):
+                from .utils import tzdb
+                if not isinstance(val, str):
+                    raise PlanError("SET time_zone takes a zone name or an offset as a string")
+                name, val = "time_zone", tzdb.check_zone(val)
+            self.session[name] = val
             return QueryResult(pa.table({}), 0.0)
         if k == "show":
             if st["s"] == "columns":
@@ -417,6 +423,9 @@ class QueryEngine:
                 return QueryResult(pa.table({"name": pa.array(keys, pa.string()),
                                              "value": pa.array([str(self.session[k]) for k in keys], pa.string())}),
                                    0.0)
+            if st["s"].lower() in ("time_zone", "timezone"):
+                return QueryResult(pa.table({"name": ["time_zone"],
+                                             "value": [str(self.session.get("time_zone") or "UTC")]}), 0.0)
             if st["s"] != "tables":
                 if st["s"] in self.session:
                     return QueryResult(pa.table({"name": [st["s"]], "value": [str(self.session[st["s"]])]}), 0.0)

@@ -372,6 +372,8 @@ class Evaluator:
         src = v.dtype
         if src == t:
             return v
+        if src.is_zoned and t.is_zoned:
+            return Column(t, v.data, v.valid)    # AT TIME ZONE on a zoned value: the same instants retagged
         if t.is_binary and src.is_string:
             from ..ops import binary as BN
             return BN.to_binary(v)           # the same buffers relabelled
@@ -582,10 +584,17 @@ class Evaluator:
             return self._mk(out, T.INT64, _and_valid(va, vc), b)
         if name == "date_trunc":
             c = args[0]
-            return Column(T.TIMESTAMP, trunc_ts(c.data.to(torch.int64), e.options[0]), c.valid)
+            return Column(e.dtype, trunc_ts(c.data.to(torch.int64), e.options[0]), c.valid)
         if name == "ts_add":
             c = args[0]
-            return Column(T.TIMESTAMP, ts_add(c.data.to(torch.int64), *e.options), c.valid)
+            return Column(e.dtype, ts_add(c.data.to(torch.int64), *e.options), c.valid)
+        if name == "date_bin":
+            c = args[0]
+            stride, origin = e.options
+            d = c.data.to(torch.int64) - origin
+            return Column(e.dtype, torch.div(d, stride, rounding_mode="floor") * stride + origin, c.valid)
+        if name in _TZ_FUNCS:
+            return self._tz_func(e, args[0])
         if name == "ts_part":
             c = args[0]
             out = ts_part(c.data.to(torch.int64), e.options[0])
@@ -749,6 +758,31 @@ class Evaluator:
               "array_except": NS.except_}[name]
         return fn(*c)
 
+    def _tz_func(self, e: Func, c: Column) -> Column:
+        """Zone-aware timestamp functions: one tz.hip kernel each on the GPU (ops/timezone.py)."""
+        from ..ops import timezone as TZ
+        name, zone = e.name, e.options[0]
+        if name == "tz_parse":
+            return _parse_tstz_host(c, e.dtype)
+        if name == "tz_to_utc":
+            return Column(e.dtype, TZ.to_utc(c.data, zone), c.valid)
+        if name == "tz_to_local":
+            return Column(e.dtype, TZ.to_local(c.data, zone), c.valid)
+        if name == "tz_trunc":
+            return Column(e.dtype, TZ.trunc(c.data, zone, e.options[1]), c.valid)
+        if name == "tz_part":
+            return Column(e.dtype, TZ.part(c.data, zone, e.options[1]), c.valid)
+        if name == "tz_add":
+            # months and days move the local wall clock (the clock time survives a DST change),
+            # the sub-day part moves the instant
+            _, months, days, us = e.options
+            out = TZ.to_utc(ts_add(TZ.to_local(c.data, zone), months, days, 0), zone)
+            return Column(e.dtype, out + us if us else out, c.valid)
+        # tz_to_char: the local wall time formatted, %z / %:z from the row's offset
+        from ..ops import digest as DG
+        local, offs = TZ.to_local(c.data, zone, want_offsets=True)
+        return DG.to_char(Column(T.TIMESTAMP, local, c.valid), e.options[1], offs)
+
     def _func_scalar(self, e: Func, args) -> Scalar:
         vals = [a.value for a in args]
         name = e.name
@@ -909,6 +943,10 @@ def iso_week(days: torch.Tensor) -> torch.Tensor:
     return torch.div(thu - jan1, 7, rounding_mode="floor") + 1
 
 
+_TZ_FUNCS = ("tz_to_utc", "tz_to_local", "tz_trunc", "tz_part", "tz_add", "tz_to_char", "tz_parse")
+_TS_TEXT_OFFSET = r"[T ]\d{2}:\d{2}.*(Z|z|[+-]\d{2}(:?\d{2})?)$"      # a time of day followed by Z / +HH / +HHMM / +HH:MM
+
+
 def trunc_ts(us: torch.Tensor, unit: str) -> torch.Tensor:
     """date_trunc over timestamps (microseconds since the epoch)."""
     step = {"microsecond": 1, "millisecond": 1000, "second": 1_000_000, "minute": 60_000_000,
@@ -1031,6 +1069,23 @@ def _parse_ts_host(v: Column) -> Column:
         raise ExecutionError(f"cannot parse timestamp: {e}") from None
     out = Column.from_arrow(ts, device=v.device)
     return Column(T.TIMESTAMP, out.data.to(torch.int64), out.valid)
+
+
+def _parse_tstz_host(v: Column, t: DataType) -> Column:
+    """CAST(string AS TIMESTAMPTZ) per row: text that carries an offset is that instant, the rest is
+    wall time in t's zone (tz_to_utc). Parsed on the host like the naive string -> timestamp cast."""
+    from ..ops import timezone as TZ
+    arr = v.to_arrow()
+    has_off = pc.fill_null(pc.match_substring_regex(arr, _TS_TEXT_OFFSET), False)
+    none = pa.nulls(len(arr), arr.type)
+    wall = _parse_ts_host(Column.from_arrow(pc.if_else(has_off, none, arr), device=v.device, dict_encode=False))
+    try:
+        inst = pc.cast(pc.if_else(has_off, arr, none), pa.timestamp("us", tz="UTC"))
+    except (pa.ArrowInvalid, pa.ArrowNotImplementedError) as e:
+        raise ExecutionError(f"cannot parse timestamp: {e}") from None
+    inst = Column.from_arrow(inst, device=v.device)
+    m = torch.from_numpy(has_off.to_numpy(zero_copy_only=False).astype(bool)).to(v.device)
+    return Column(t, torch.where(m, inst.data.to(torch.int64), TZ.to_utc(wall.data, t.tz)), v.valid)
 
 
 def _convert_scalar(x, src: DataType, t: DataType):

@@ -413,6 +413,11 @@ class _Gen:
             return v
         if t.kind == "bool":
             return self.bind("bool", f"({v[0]}) != 0"), v[1], t
+        if t.kind == "date32" and src.kind == "timestamp":      # the day of the instant, floored
+            return self.bind("i32", f"(i32)(((i64)({v[0]}) >= 0 ? (i64)({v[0]}) : (i64)({v[0]}) - 86399999999LL) "
+                                    f"/ 86400000000LL)"), v[1], t
+        if t.kind == "timestamp" and src.kind == "date32":      # the day's midnight
+            return self.bind("i64", f"(i64)({v[0]}) * 86400000000LL"), v[1], t
         x = self.conv(v, t if t.kind != "date32" else T.INT32)
         return self.bind(_ct(t), f"({_ct(t)})({x})"), v[1], t
 

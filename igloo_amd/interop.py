@@ -51,6 +51,8 @@ def _fmt(dt: T.DataType) -> str:
     k = dt.kind
     if dt.is_decimal:
         return f"d:{max(dt.precision, 1)},{dt.scale}"
+    if k == "timestamp":
+        return f"tsu:{dt.tz or ''}"        # int64 microseconds; the zone name rides in the format string
     return {"int8": "c", "int16": "s", "int32": "i", "int64": "l", "uint8": "C", "float32": "f", "float64": "g",
             "bool": "b", "date32": "tdD", "null": "n"}.get(k) or ("U" if dt.is_string else "Z" if dt.is_binary else None) or \
         _unsupported(dt)
@@ -95,7 +97,7 @@ def _column_specs(c: Column, name: str, nullable: bool) -> Tuple[tuple, tuple]:
         return (_fmt(dt), name, nullable, [], None), (n, null_count, [validity, addr(wide)], [], None, keep)
     data = c.data
     want = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
-            "float32": torch.float32, "float64": torch.float64, "date32": torch.int32, "uint8": torch.uint8}
+            "float32": torch.float32, "float64": torch.float64, "date32": torch.int32, "uint8": torch.uint8, "timestamp": torch.int64}
     if dt.kind in want and data.dtype != want[dt.kind]:
         data = data.to(want[dt.kind])
     return (_fmt(dt), name, nullable, [], None), (n, null_count, [validity, addr(data)], [], None, keep)

@@ -73,8 +73,9 @@ def uuid_column(n: int, device) -> Column:
     return _fixed_width(chars, n, 36, None)
 
 
-def py_strftime(us: int, fmt: str) -> str:
-    """Host twin of strfmt.hip (chrono's subset used by to_char)."""
+def py_strftime(us: int, fmt: str, offset: int = None) -> str:
+    """Host twin of strfmt.hip (chrono's subset used by to_char). ``offset``: the UTC offset
+    in seconds of a zoned value (``us`` is then local wall time) for %z / %:z."""
     t = datetime.datetime(1970, 1, 1) + datetime.timedelta(microseconds=int(us))
     out, i = [], 0
     days = ["Sunday", "Monday", "Tuesday", "Wednesday", "Thursday", "Friday", "Saturday"]
@@ -89,6 +90,15 @@ def py_strftime(us: int, fmt: str) -> str:
             continue
         s = fmt[i + 1]
         i += 2
+        if offset is not None and (s == "z" or (s == ":" and fmt[i:i + 1] == "z")):
+            from .timezone import format_offset
+            out.append(format_offset(offset, colon=s == ":"))
+            i += s == ":"
+            continue
+        if s == "#" and fmt[i:i + 1] == "f" and offset is not None:
+            out.append(f".{t.microsecond:06d}" if t.microsecond else "")
+            i += 1
+            continue
         if s == "." and i <= len(fmt):
             if fmt[i:i + 1] == "f":
                 out.append("." + f"{t.microsecond * 1000:09d}")
@@ -110,13 +120,14 @@ def py_strftime(us: int, fmt: str) -> str:
              "h": months[t.month - 1][:3], "B": months[t.month - 1], "u": str(dow or 7), "w": str(dow),
              "F": f"{t.year:04d}-{t.month:02d}-{t.day:02d}", "T": f"{t.hour:02d}:{t.minute:02d}:{t.second:02d}",
              "R": f"{t.hour:02d}:{t.minute:02d}", "D": f"{t.month:02d}/{t.day:02d}/{t.year % 100:02d}",
-             "s": str(us // 1_000_000), "%": "%"}.get(s)
+             "s": str(us // 1_000_000 - (offset or 0)), "%": "%"}.get(s)
         out.append(m if m is not None else "%" + s)
     return "".join(out)
 
 
-def to_char(col: Column, fmt: str) -> Column:
-    """to_char(date | timestamp, format) with chrono's strftime syntax."""
+def to_char(col: Column, fmt: str, offsets: torch.Tensor = None) -> Column:
+    """to_char(date | timestamp, format) with chrono's strftime syntax. ``offsets``
+    (int32 seconds per row): the values are local wall time of a zoned column."""
     from .select import offsets_from_lengths
     is_date = col.dtype.kind == "date32"
     n = len(col)
@@ -124,16 +135,18 @@ def to_char(col: Column, fmt: str) -> Column:
         vals = col.data.tolist()
         mult = 86_400_000_000 if is_date else 1
         ok = col.valid.tolist() if col.valid is not None else [True] * n
-        out = [py_strftime(v * mult, fmt) if k else None for v, k in zip(vals, ok)]
+        offs = offsets.tolist() if offsets is not None else [None] * n
+        out = [py_strftime(v * mult, fmt, o) if k else None for v, k, o in zip(vals, ok, offs)]
         return Column.from_arrow(pa.array(out, pa.large_string()), device=col.device, dict_encode=False)
     v = col.data.contiguous()
     b = fmt.encode("utf-8")
     N = native()
     s = stream(v)
     lens = torch.empty(max(n, 1), dtype=torch.int64, device=v.device)
-    launch("strfmt").strfmt_lengths(b, is_date, ptr(v), n, ptr(lens), s)
+    offs = offsets.contiguous() if offsets is not None else None
+    launch("strfmt").strfmt_lengths(b, is_date, ptr(v), ptr(offs), n, ptr(lens), s)
     off, total = offsets_from_lengths(lens[:n])
     chars = torch.empty(max(total, 1), dtype=torch.uint8, device=v.device)[:total]
     if total:
-        N.strfmt_write(b, is_date, ptr(v), n, ptr(off), int(chars.numel()), ptr(chars), s)
+        N.strfmt_write(b, is_date, ptr(v), ptr(offs), n, ptr(off), int(chars.numel()), ptr(chars), s)
     return Column(T.UTF8, chars, col.valid, offsets=off)

@@ -121,6 +121,11 @@ class Binder:
         self.ids = ids or IdGen()
         self.session = session or {}
 
+    @property
+    def session_tz(self) -> str:
+        """The session time zone (SET time_zone): what TIMESTAMPTZ type names and casts take."""
+        return str(self.session.get("time_zone") or "UTC")
+
     # =================================================================== query
     def bind_query(self, q: dict, outer: Optional[Scope] = None, ctes: Optional[dict] = None) -> BoundQuery:
         ctes = dict(ctes or {})
@@ -819,7 +824,10 @@ class Binder:
             return Not(e) if node.get("neg") else e
         if k == "cast":
             x = self.bind_expr(node["c"][0], scope, allow_agg)
-            t = T.parse_type_name(node["type"])
+            t = T.parse_type_name(node["type"], self.session_tz)
+            if t.is_zoned:
+                from ..utils import tzdb
+                tzdb.check_zone(t.tz)
             return self._cast(x, t)
         if k == "case":
             return self._case(node, scope, allow_agg)
@@ -902,7 +910,34 @@ class Binder:
             return x
         if isinstance(x, Lit):
             return _fold_cast(x, t)
+        src = x.dtype
+        if src.is_zoned or t.is_zoned:
+            return self._cast_zoned(x, t)
         return Cast(x, t)
+
+    def _cast_zoned(self, x: Expr, t: DataType) -> Expr:
+        """Casts from or to TIMESTAMP WITH TIME ZONE (x is no literal)."""
+        src = x.dtype
+        if src.is_zoned:
+            if t.is_zoned:
+                return Cast(x, t)                    # the same instants under another tag: nothing runs
+            if t.kind == "timestamp":
+                return Func("tz_to_local", [x], T.TIMESTAMP, (src.tz,))
+            if t.kind == "date32":
+                return Cast(Func("tz_to_local", [x], T.TIMESTAMP, (src.tz,)), DATE32)
+            if t.is_string:
+                return Func("tz_to_char", [x], UTF8, (src.tz, _TSTZ_TEXT))
+            if t.kind == "int64":
+                return Cast(x, t)
+            raise PlanError(f"cannot cast {src} to {t}")
+        if src.kind in ("timestamp", "date32"):
+            return Func("tz_to_utc", [self._to_ts(x)], t, (t.tz,))
+        if src.is_string:
+            # per row: text with an offset is that instant, text without one is wall time in t's zone
+            return Func("tz_parse", [x], t, (t.tz,))
+        if src.kind == "null":
+            return Cast(x, t)
+        raise PlanError(f"cannot cast {src} to {t}")
 
     def _coerce_lit(self, v: Lit, t: DataType) -> Lit:
         if TPL.tracking(v):
@@ -932,7 +967,9 @@ class Binder:
         # literal coercion towards the column type
         if lt != rt:
             if isinstance(r, Lit) and not isinstance(l, Lit):
-                if lt.kind == "timestamp" and (rt.is_string or rt.kind == "date32"):
+                if lt.is_zoned and rt.is_string:
+                    r = _fold_cast(r, lt)       # with an offset: that instant; without: wall time in lt's zone
+                elif lt.kind == "timestamp" and (rt.is_string or rt.kind == "date32"):
                     r = _fold_cast(r, T.TIMESTAMP)
                 elif rt.kind == "timestamp" and lt.kind == "date32":
                     l = self._to_ts(l)
@@ -941,7 +978,9 @@ class Binder:
                 elif lt.is_string and not rt.is_string and TPL.peek(r) is not None:
                     r = _fold_cast(r, UTF8)
             elif isinstance(l, Lit) and not isinstance(r, Lit):
-                if rt.kind == "timestamp" and (lt.is_string or lt.kind == "date32"):
+                if rt.is_zoned and lt.is_string:
+                    l = _fold_cast(l, rt)
+                elif rt.kind == "timestamp" and (lt.is_string or lt.kind == "date32"):
                     l = _fold_cast(l, T.TIMESTAMP)
                 elif rt.kind == "date32" and lt.is_string:
                     l = TPL.derive(lambda a: Lit(date_to_days(a.value), DATE32), l)
@@ -973,6 +1012,11 @@ class Binder:
                         return Func("add_months", [l], DATE32, (months, days))
                     return BinOp("+", l, Lit(days, INT32), DATE32)
                 x = self._to_ts(l)
+                if x.dtype.is_zoned:
+                    # months and days move the local wall clock, the rest moves the instant
+                    if months or days:
+                        return Func("tz_add", [x], x.dtype, (x.dtype.tz, months, days, us))
+                    return Func("ts_add", [x], x.dtype, (0, 0, us))
                 if isinstance(x, Lit):
                     if x.value is None:
                         return Lit(None, T.TIMESTAMP)
@@ -987,6 +1031,8 @@ class Binder:
             raise NotSupported(f"interval arithmetic {lt} {op} {rt}")
         if lt.kind == "timestamp" or rt.kind == "timestamp":
             if op == "-" and lt.kind == "timestamp" and rt.kind in ("timestamp", "date32"):
+                if lt.is_zoned != rt.is_zoned:
+                    raise PlanError(f"cannot subtract {rt} from {lt}: convert one side with AT TIME ZONE")
                 return BinOp("-", l, self._to_ts(r), INT64)
             raise PlanError(f"cannot apply {op} to {lt} and {rt}")
         if lt.kind == "date32" or rt.kind == "date32":
@@ -1221,6 +1267,10 @@ class Binder:
                 x = self._coerce(x, T.TIMESTAMP)
             if x.dtype.kind not in ("date32", "timestamp"):
                 raise PlanError(f"{name}() formats dates and timestamps, got {x.dtype}")
+            if x.dtype.is_zoned:
+                if "%Z" in args[1].value.replace("%%", ""):
+                    raise NotSupported(f"{name}(): %Z (zone abbreviations); use %z or %:z")
+                return Func("tz_to_char", [x], UTF8, (x.dtype.tz, args[1].value))
             if isinstance(x, Lit):
                 from ..ops.digest import py_strftime
                 mult = 86_400_000_000 if x.dtype.kind == "date32" else 1
@@ -1541,6 +1591,8 @@ class Binder:
             raise NotSupported(f"EXTRACT({field})")
         if x.dtype.is_string:
             x = self._coerce(x, T.TIMESTAMP if field in time_fields else DATE32)
+        if x.dtype.is_zoned and field != "epoch":
+            return Func("tz_part", [x], INT32, (x.dtype.tz, field))      # the field of the local wall time
         if x.dtype.kind == "timestamp" or field in time_fields:
             x = self._to_ts(x)
             rt = FLOAT64 if field == "epoch" else INT32
@@ -1775,10 +1827,56 @@ class Binder:
             if x.dtype.is_string:
                 x = self._coerce(x, T.TIMESTAMP)
             x = self._to_ts(x)
+            if x.dtype.is_zoned:
+                if unit in ("microsecond", "millisecond"):         # below every offset's granularity
+                    return Func("date_trunc", [x], x.dtype, (unit,))
+                return Func("tz_trunc", [x], x.dtype, (x.dtype.tz, unit))
             if isinstance(x, Lit):
                 from ..exec.expr_eval import trunc_ts_py
                 return Lit(None if x.value is None else trunc_ts_py(x.value, unit), T.TIMESTAMP)
             return Func("date_trunc", [x], T.TIMESTAMP, (unit,))
+        if name == "at_time_zone":
+            _nargs(name, args, 2)
+            return self._at_time_zone(args[0], args[1])
+        if name == "to_local_time":
+            _nargs(name, args, 1)
+            x = args[0]
+            if x.dtype.is_string:
+                x = self._coerce(x, T.TIMESTAMP)
+            if x.dtype.kind != "timestamp":
+                raise PlanError(f"to_local_time() takes a timestamp, got {x.dtype}")
+            return Func("tz_to_local", [x], T.TIMESTAMP, (x.dtype.tz,)) if x.dtype.is_zoned else x
+        if name == "date_bin":
+            if len(args) not in (2, 3):
+                raise PlanError("date_bin(stride, source [, origin]) takes 2 or 3 arguments")
+            if not isinstance(args[0], Lit) or args[0].dtype != INTERVAL or args[0].value is None:
+                raise NotSupported("date_bin(): the stride must be an INTERVAL literal")
+            months, days, us = args[0].value
+            if months:
+                raise NotSupported("date_bin() with a month stride (day-time strides only)")
+            stride = days * 86_400_000_000 + us
+            if stride <= 0:
+                raise PlanError("date_bin(): the stride must be positive")
+            x = args[1]
+            if x.dtype.is_string:
+                x = self._coerce(x, T.TIMESTAMP)
+            x = self._to_ts(x)
+            origin = 0
+            if len(args) == 3:
+                o = args[2]
+                if not isinstance(o, Lit):
+                    raise NotSupported("date_bin(): the origin must be a constant")
+                if o.dtype.is_string:
+                    o = _fold_cast(o, x.dtype)
+                elif o.dtype.kind == "date32":
+                    o = self._to_ts(o)
+                if o.dtype.kind != "timestamp" or o.dtype.is_zoned != x.dtype.is_zoned:
+                    raise PlanError(f"date_bin(): origin {o.dtype} does not match the source {x.dtype} "
+                                    f"(convert one with AT TIME ZONE)")
+                if o.value is None:
+                    return Lit(None, x.dtype)
+                origin = int(o.value)
+            return Func("date_bin", [x], x.dtype, (stride, origin))
         if name in ("to_timestamp", "to_timestamp_micros", "to_timestamp_millis", "to_timestamp_seconds",
                     "from_unixtime"):
             x = args[0]
@@ -1795,6 +1893,24 @@ class Binder:
         if name == "make_date":
             return Func("make_date", [self._coerce(a, INT64) for a in args[:3]], DATE32)
         raise NotSupported(f"function {name}()")
+
+    def _at_time_zone(self, x: Expr, zone: Expr) -> Expr:
+        """x AT TIME ZONE 'zone': a naive timestamp (or a date's midnight) is wall time in the
+        zone and becomes an instant; a zoned one is the same instant under the new tag."""
+        from ..utils import tzdb
+        if not isinstance(zone, Lit) or not isinstance(zone.value, str):
+            raise NotSupported("AT TIME ZONE with a zone that is not a string literal (column-valued zones)")
+        tz = tzdb.check_zone(zone.value)      # (reading .value keys a statement template on the zone)
+        t = T.TIMESTAMPTZ(tz)
+        if x.dtype.is_string:
+            x = self._coerce(x, T.TIMESTAMP)
+        if x.dtype.kind == "null":
+            return Lit(None, t)
+        if x.dtype.kind not in ("timestamp", "date32"):
+            raise PlanError(f"AT TIME ZONE applies to timestamps and dates, got {x.dtype}")
+        if x.dtype.is_zoned:
+            return x if x.dtype == t else Cast(x, t)
+        return Func("tz_to_utc", [self._to_ts(x)], t, (tz,))
 
     def _now_us(self) -> int:
         now = getattr(self, "_now", None)
@@ -2060,7 +2176,7 @@ def arrow_type_name(t: DataType) -> str:
     if k == "decimal":
         return f"Decimal128({t.precision}, {t.scale})"
     if k == "timestamp":
-        return "Timestamp(Microsecond, None)"
+        return f'Timestamp(us, "{t.tz}")' if t.tz is not None else "Timestamp(Microsecond, None)"
     if k == "list":
         return f"List(Field {{ name: \"item\", data_type: {arrow_type_name(t.child)}, nullable: true, dict_id: 0, " \
                f"dict_is_ordered: false, metadata: {{}} }})"
@@ -2347,6 +2463,8 @@ def _fold_cast(v: Lit, t: DataType) -> Lit:
     if x is None:
         return Lit(None, t)
     src = v.dtype
+    if src.is_zoned or t.is_zoned:
+        return _fold_cast_zoned(v, t)
     try:
         if t.is_decimal:
             if src.is_decimal:
@@ -2405,6 +2523,54 @@ def _fold_cast(v: Lit, t: DataType) -> Lit:
     except (ValueError, ArithmeticError) as e:
         raise PlanError(f"cannot cast {v.sql()} to {t}") from e
     return Lit(x, t)
+
+
+#: CAST(timestamptz AS VARCHAR): YYYY-MM-DDTHH:MM:SS[.ffffff]+HH:MM
+_TSTZ_TEXT = "%Y-%m-%dT%H:%M:%S%#f%:z"
+
+
+def _fold_cast_zoned(v: Lit, t: DataType) -> Lit:
+    """Constant casts from or to TIMESTAMP WITH TIME ZONE, through the host twins of the tz kernels."""
+    from ..ops import timezone as TZ
+    x, src = v.value, v.dtype
+    if src.is_zoned:
+        if t.kind == "timestamp":
+            return Lit(int(x) if t.is_zoned else TZ.to_local_py(x, src.tz), t)
+        if t.kind == "date32":
+            return Lit(TZ.to_local_py(x, src.tz) // 86_400_000_000, t)
+        if t.is_string:
+            from ..ops.digest import py_strftime
+            return Lit(py_strftime(TZ.to_local_py(x, src.tz), _TSTZ_TEXT, TZ.offset_py(x, src.tz)), t)
+        if t.kind == "int64":
+            return Lit(int(x), t)
+        raise PlanError(f"cannot cast {v.sql()} ({src}) to {t}")
+    if src.is_string:
+        try:
+            dt = datetime.datetime.fromisoformat(_iso_text(x))
+        except ValueError as e:
+            raise PlanError(f"cannot cast {v.sql()} to {t}") from e
+        if dt.tzinfo is not None:       # an offset in the text: that instant
+            us = (dt - datetime.datetime(1970, 1, 1, tzinfo=datetime.timezone.utc)) // datetime.timedelta(microseconds=1)
+            return Lit(us, t)
+        wall = (dt - datetime.datetime(1970, 1, 1)) // datetime.timedelta(microseconds=1)
+        return Lit(TZ.to_utc_py(wall, t.tz), t)
+    if src.kind == "timestamp":
+        return Lit(TZ.to_utc_py(int(x), t.tz), t)
+    if src.kind == "date32":
+        return Lit(TZ.to_utc_py(int(x) * 86_400_000_000, t.tz), t)
+    raise PlanError(f"cannot cast {v.sql()} ({src}) to {t}")
+
+
+def _iso_text(s: str) -> str:
+    """Timestamp text as ``datetime.fromisoformat`` reads it: 'Z', '+HH' and '+HHMM' offsets spelled '+HH:MM'."""
+    import re
+    s = s.strip().replace("T", " ")
+    if s[-1:] in ("Z", "z"):
+        return s[:-1].rstrip() + "+00:00"
+    m = re.search(r"(?<=\d)([+-])(\d{2})(?::?(\d{2}))?$", s)
+    if m and ":" in s[:m.start()]:          # an offset follows a time of day, never a bare date
+        return s[:m.start()] + f"{m.group(1)}{m.group(2)}:{m.group(3) or '00'}"
+    return s
 
 
 def _round_div(a: int, b: int) -> int:

@@ -51,7 +51,8 @@ DATETIME: Dict[str, str] = {
     "to_timestamp": "to_timestamp(n)", "to_timestamp_seconds": "to_timestamp_seconds(n)",
     "to_timestamp_millis": "to_timestamp_millis(n)", "to_timestamp_micros": "to_timestamp_micros(n)",
     "from_unixtime": "from_unixtime(n)", "to_unixtime": "to_unixtime(ts)", "to_date": "to_date('2024-01-02')",
-    "make_date": "make_date(2020, n, 1)",
+    "make_date": "make_date(2020, n, 1)", "date_bin": "date_bin(interval '15 minutes', ts)",
+    "to_local_time": "to_local_time(ts at time zone '+02:00')",
 }
 SYSTEM: Dict[str, str] = {
     "coalesce": "coalesce(s, 'none')", "ifnull": "ifnull(n, 0)", "nvl": "nvl(n, -1)", "nullif": "nullif(n, 2)",

@@ -45,6 +45,7 @@ class DataType:
     scale: int = 0
     child: Optional["DataType"] = None     # LIST element type
     fields: Tuple = ()                     # STRUCT ((name, DataType), ...); MAP (("key", k), ("value", v))
+    tz: Optional[str] = None               # TIMESTAMP WITH TIME ZONE: the zone name (storage stays UTC microseconds)
 
     @property
     def is_nested(self) -> bool:
@@ -94,6 +95,11 @@ class DataType:
     def is_temporal(self) -> bool:
         return self.kind in ("date32", "timestamp")
 
+    @property
+    def is_zoned(self) -> bool:
+        """TIMESTAMP WITH TIME ZONE: an instant (int64 UTC microseconds, as TIMESTAMP) tagged with a zone."""
+        return self.kind == "timestamp" and self.tz is not None
+
     # --------------------------------------------------------------- conversion
     @property
     def torch_dtype(self) -> torch.dtype:
@@ -114,7 +120,7 @@ class DataType:
         if k == "binary":
             return pa.large_binary()
         if k == "timestamp":
-            return pa.timestamp("us")
+            return pa.timestamp("us", tz=self.tz)
         return _ARROW[k]
 
     def __str__(self) -> str:
@@ -126,6 +132,8 @@ class DataType:
             return "Struct(" + ", ".join(f"{n} {t}" for n, t in self.fields) + ")"
         if self.kind == "map":
             return f"Map({self.key}, {self.value})"
+        if self.tz is not None:
+            return f'Timestamp(us, "{self.tz}")'
         return _NAMES.get(self.kind, self.kind)
 
     __repr__ = __str__
@@ -141,6 +149,12 @@ FLOAT64 = DataType("float64")
 DATE32 = DataType("date32")
 TIMESTAMP = DataType("timestamp")
 UTF8 = DataType("utf8")
+
+
+def TIMESTAMPTZ(zone: str) -> DataType:
+    return DataType("timestamp", tz=zone)
+
+
 BINARY = DataType("binary")
 NULL = DataType("null")
 
@@ -241,7 +255,7 @@ def from_arrow_type(t: pa.DataType) -> DataType:
     if pa.types.is_date32(t) or pa.types.is_date64(t):
         return DATE32
     if pa.types.is_timestamp(t):
-        return TIMESTAMP
+        return TIMESTAMPTZ(t.tz) if t.tz else TIMESTAMP
     if pa.types.is_decimal(t):
         return DECIMAL(t.precision, t.scale)
     if pa.types.is_string(t) or pa.types.is_large_string(t) or pa.types.is_string_view(t):
@@ -254,9 +268,14 @@ def from_arrow_type(t: pa.DataType) -> DataType:
     raise PlanError(f"unsupported Arrow type {t}")
 
 
-def parse_type_name(name: str) -> DataType:
-    """SQL type name (as produced by the parser) -> DataType."""
+def parse_type_name(name: str, session_tz: str = "UTC") -> DataType:
+    """SQL type name (as produced by the parser) -> DataType. TIMESTAMPTZ /
+    TIMESTAMP WITH TIME ZONE take the session zone."""
     n = name.upper().replace(" ", "")
+    if n in ("TIMESTAMPTZ", "TIMESTAMPWITHTIMEZONE"):
+        return TIMESTAMPTZ(session_tz)
+    if n == "TIMESTAMPWITHOUTTIMEZONE":
+        return TIMESTAMP
     base, args = n, []
     if "(" in n:
         base = n[: n.index("(")]
@@ -312,9 +331,13 @@ def common_numeric(a: DataType, b: DataType) -> DataType:
     if a.is_integer and b.is_integer:
         order = INT_KINDS
         return DataType(order[max(order.index(a.kind), order.index(b.kind))])
+    if a.is_zoned != b.is_zoned and a.kind == b.kind:
+        raise PlanError(f"cannot mix {a} and {b}: convert one side with AT TIME ZONE")
     if a.kind == b.kind:
-        return a
+        return a                       # two zones: the same instants, the first zone's tag
     if {a.kind, b.kind} <= {"date32", "timestamp"}:
+        if a.is_zoned or b.is_zoned:
+            raise PlanError(f"cannot mix {a} and {b}: convert the date with AT TIME ZONE")
         return TIMESTAMP
     if a.is_string and b.is_temporal:
         return b

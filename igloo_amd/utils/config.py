@@ -40,6 +40,9 @@ class IglooConfig:
     tables: Dict[str, Dict[str, Any]] = field(default_factory=dict)
     auth_token: Optional[str] = None
     log_level: str = "warning"
+    # zoneinfo directory searched first for time zones (utils/tzdb.py). Its environment name is IGLOO_TZDIR,
+    # the switch tzdb itself reads, and ranks like every other setting: file < environment < flags
+    tz_dir: Optional[str] = None
     fault: Optional[str] = None   # fault-injection spec (utils/faults.py), e.g. "drop_heartbeat"
 
     def to_dict(self) -> dict:
@@ -67,7 +70,7 @@ def load_config(path: Optional[str] = None, overrides: Optional[dict] = None) ->
         data.update(_parse_file(path))
     names = {f.name: f for f in fields(IglooConfig)}
     for k, f in names.items():
-        env = os.environ.get("IGLOO_" + k.upper())
+        env = os.environ.get("IGLOO_TZDIR" if k == "tz_dir" else "IGLOO_" + k.upper())
         if env is not None:
             if f.type in ("int", int):
                 data[k] = int(env)
@@ -81,7 +84,10 @@ def load_config(path: Optional[str] = None, overrides: Optional[dict] = None) ->
     unknown = set(data) - set(names)
     if unknown:
         raise ValueError(f"unknown config keys: {sorted(unknown)}")
-    return IglooConfig(**data)
+    cfg = IglooConfig(**data)
+    from . import tzdb
+    tzdb.set_tz_dir(cfg.tz_dir)      # the loaded configuration decides: set, or cleared when it names none
+    return cfg
 
 
 def register_config_tables(engine, cfg: IglooConfig):

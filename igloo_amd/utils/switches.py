@@ -49,7 +49,11 @@ Other variables (each read in one place):
   device memory budgets;
 * ``IGLOO_PARQUET_READ_THREADS``, ``IGLOO_PARQUET_BATCH_BYTES``: cold-scan I/O;
 * ``IGLOO_SUPERVISOR_ID``: set by the node supervisor for its workers;
-* ``IGLOO_<setting>`` for every field of utils/config.py ``IglooConfig``.
+* ``IGLOO_TZDIR``: a zoneinfo directory (TZif files) searched before ``zoneinfo.TZPATH`` and the
+  ``tzdata`` package for time zones (utils/tzdb.py). It is also the environment name of the ``tz_dir``
+  setting of utils/config.py (there is no ``IGLOO_TZ_DIR``) and ranks there like every setting: config
+  file < this variable < command line; a directory set through ``tzdb.set_tz_dir`` wins over the variable;
+* ``IGLOO_<setting>`` for every field of utils/config.py ``IglooConfig`` (``tz_dir``: ``IGLOO_TZDIR``).
 """
 from __future__ import annotations
 
@@ -73,7 +77,7 @@ DEBUG: Dict[str, str] = _parse(os.environ.get("IGLOO_DEBUG"))
 ENV = ("IGLOO_DEBUG", "IGLOO_LOG", "IGLOO_FAULT", "IGLOO_JIT", "IGLOO_JIT_CACHE", "IGLOO_JIT_AOT",
        "IGLOO_OFFLOAD_ARCH", "IGLOO_GRAPHS", "IGLOO_FORCE_SPMD", "IGLOO_COMM_BACKEND", "IGLOO_DEVICE_BUDGET_GB",
        "IGLOO_HBM_BUDGET_GB", "IGLOO_PACK_BUDGET_GB", "IGLOO_PARQUET_READ_THREADS", "IGLOO_PARQUET_BATCH_BYTES",
-       "IGLOO_SUPERVISOR_ID")
+       "IGLOO_SUPERVISOR_ID", "IGLOO_TZDIR")
 
 
 def debug(token: str) -> bool:
