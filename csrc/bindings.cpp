@@ -556,6 +556,8 @@ PYBIND11_MODULE(_native, m) {
   m.def("fmt_lengths", raw<&kern::fmt_lengths>);
   m.def("fmt_write", raw<&kern::fmt_write>);
   m.def("str_parse", raw<&kern::str_parse>);
+  m.def("try_parse", raw<&kern::try_parse>);
+  m.def("cast_checked", raw<&kern::cast_checked>);
   m.def("str_prefix_keys", raw<&kern::str_prefix_keys>);
   m.def("str_hash64", raw<&kern::str_hash64>);
   m.def("str_like_segments", raw<&kern::str_like_segments>);

@@ -333,6 +333,15 @@ void fmt_write(const void* vals, int kind, int64_t n, int scale, const uint8_t* 
                uint8_t* out, hipStream_t stream);
 void str_parse(const int64_t* off, const uint8_t* chars, int64_t n, const uint8_t* valid, int kind, int scale,
                void* out, int* err, hipStream_t stream);
+// TRY_CAST (trycast.hip): a validity byte per row, no error flag, no readback.
+// try_parse kind: 0 int64, 1 int32, 2 decimal(precision, scale) -> int64, 3 date32, 4 float64, 5 bool,
+// 6 int16, 7 int8, 8 float32, 9 timestamp; out holds n values of the kind's storage type.
+void try_parse(const int64_t* off, const uint8_t* chars, int64_t n, const uint8_t* valid, int kind, int scale,
+               int precision, void* out, uint8_t* valid_out, hipStream_t stream);
+// cast_checked kinds (castcheck.h CastKind): 0-3 int8/16/32/64, 4 float32, 5 float64, 6 decimal (int64 at a
+// scale), 7 wide (int128 as (low, high) int64 words per row; source only). Targets: 0-3 and 6.
+void cast_checked(const void* src, int src_kind, int src_scale, int64_t n, const uint8_t* valid_in, int dst_kind,
+                  int dst_scale, int dst_precision, void* dst, uint8_t* valid_out, hipStream_t stream);
 // LIKE made of '%'-separated literals (no '_'): segments concatenated in `seg`
 // with offsets seg_off[nseg+1]; anchor_start/end = pattern does not begin/end with '%';
 // min_seg = the shortest segment's length (host-known: picks the kernel)

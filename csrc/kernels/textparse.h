@@ -388,6 +388,72 @@ __device__ inline bool parse_date(const uint8_t* p, const uint8_t* e, int32_t* o
   return true;
 }
 
+// two ASCII digits at p -> 0..99, or -1
+__device__ inline int parse_2digits(const uint8_t* p) {
+  const unsigned a = (unsigned)p[0] - '0', b = (unsigned)p[1] - '0';
+  return (a > 9 || b > 9) ? -1 : (int)(a * 10 + b);
+}
+
+// Naive timestamp text -> microseconds since 1970-01-01T00:00:00:
+//   YYYY-MM-DD [ ('T' | 't' | ' ') HH:MM [ :SS [ .f{1,9} ] ] ] [ 'Z' | 'z' | +-HH | +-HH:MM | +-HHMM ]
+// Years 0001-9999, a real calendar day, HH <= 23, MM and SS <= 59 (no leap second), offset
+// hours <= 23 and minutes <= 59. Fraction digits past the sixth are dropped; an offset shifts
+// the instant to UTC. Every field sits at a fixed position once the date is read; any other
+// byte, before, between or after, rejects the text.
+__device__ inline bool parse_timestamp(const uint8_t* p, const uint8_t* e, int64_t* out) {
+  const int64_t n = e - p;
+  int32_t days = 0;
+  if (n < 10 || !parse_date(p, p + 10, &days)) return false;
+  if (p[0] == '0' && p[1] == '0' && p[2] == '0' && p[3] == '0') return false;
+  int64_t pos = 10, secs = 0, frac = 0;
+  if (pos < n && (p[pos] == 'T' || p[pos] == 't' || p[pos] == ' ')) {
+    if (n < pos + 6 || p[pos + 3] != ':') return false;
+    const int hh = parse_2digits(p + pos + 1), mi = parse_2digits(p + pos + 4);
+    if (hh < 0 || hh > 23 || mi < 0 || mi > 59) return false;
+    secs = hh * 3600 + mi * 60;
+    pos += 6;
+    if (pos < n && p[pos] == ':') {
+      if (n < pos + 3) return false;
+      const int ss = parse_2digits(p + pos + 1);
+      if (ss < 0 || ss > 59) return false;
+      secs += ss;
+      pos += 3;
+      if (pos < n && p[pos] == '.') {
+        ++pos;
+        int nd = 0;
+        int64_t unit = 100000;
+        for (; pos < n && nd < 9; ++pos, ++nd) {
+          const unsigned d = (unsigned)p[pos] - '0';
+          if (d > 9) break;
+          frac += d * unit;               // unit reaches 0 after six digits: the rest is dropped
+          unit /= 10;
+        }
+        if (nd == 0) return false;
+      }
+    }
+  }
+  int64_t shift = 0;
+  if (pos < n) {
+    const uint8_t c = p[pos];
+    const int64_t rest = n - pos - 1;
+    if (c == 'Z' || c == 'z') {
+      if (rest != 0) return false;
+    } else if (c == '+' || c == '-') {
+      if (rest != 2 && rest != 4 && rest != 5) return false;
+      if (rest == 5 && p[pos + 3] != ':') return false;
+      const int oh = parse_2digits(p + pos + 1);
+      const int om = rest == 2 ? 0 : parse_2digits(p + pos + (rest == 5 ? 4 : 3));
+      if (oh < 0 || oh > 23 || om < 0 || om > 59) return false;
+      shift = oh * 3600 + om * 60;
+      if (c == '-') shift = -shift;
+    } else {
+      return false;
+    }
+  }
+  *out = ((int64_t)days * 86400 + secs - shift) * 1000000 + frac;
+  return true;
+}
+
 // days since 1970-01-01 -> civil date (H. Hinnant's algorithm)
 __device__ inline void civil_from_days(int64_t z, int64_t* y, int* m, int* d) {
   z += 719468;

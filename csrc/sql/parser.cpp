@@ -1196,6 +1196,16 @@ class Parser {
         if (lower(name) == "map" && t.kind == Token::Ident && isOp("{")) return mapLiteral();
         if (isOp("(") && t.kind == Token::Ident) {
           if (name == "trim") return trimCall();
+          if (lower(name) == "try_cast") {  // TRY_CAST(x AS t): the cast node, flagged; NULL where CAST raises
+            ++p_;
+            auto c = make("cast");
+            c->kids.push_back(expr());
+            expectKw("AS");
+            c->flags["type"] = typeName();
+            c->flags["try"] = "1";
+            expectOp(")");
+            return c;
+          }
           if (name == "position") {  // POSITION(needle IN haystack) -> strpos(haystack, needle)
             ++p_;
             NodeP needle = additive();

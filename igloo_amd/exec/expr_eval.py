@@ -369,6 +369,9 @@ class Evaluator:
         if isinstance(v, Scalar):
             from ..sql.binder import _fold_cast
             return Scalar(_fold_cast(Lit(v.value, v.dtype), t).value, t)
+        return self._cast_column(v, t)
+
+    def _cast_column(self, v: Column, t: DataType) -> Column:
         src = v.dtype
         if src == t:
             return v
@@ -493,8 +496,26 @@ class Evaluator:
             return Scalar((rx.fullmatch(v.value) is not None) != e.negated, T.BOOL)
         return Column(T.BOOL, S.like(v, e.pattern, e.case_insensitive, e.negated, e.escape), v.valid)
 
+    def _try_cast(self, e: Func, b: Batch) -> Value:
+        """TRY_CAST: the validity-writing kernels (ops/trycast.py) for the pairs that can fail, CAST's own
+        conversion for the rest. No readback and no host step on the GPU."""
+        from ..ops import trycast as TC
+        v = self.eval(e.args[0], b)
+        t = e.dtype
+        if isinstance(v, Scalar):
+            from ..sql.binder import _fold_try_cast
+            return Scalar(_fold_try_cast(Lit(v.value, v.dtype), t).value, t)
+        src = v.dtype
+        if src.is_string and TC.can_parse(t):
+            return TC.try_parse(v, t)
+        if src.is_numeric and (TC.can_fail(src, t) or (v.is_wide and (t.is_integer or t.is_decimal))):
+            return TC.cast_checked(v, t)
+        return self._cast_column(v, t)
+
     def _Func(self, e: Func, b: Batch) -> Value:
         name = e.name
+        if name == "try_cast":
+            return self._try_cast(e, b)
         args = [self.eval(a, b) for a in e.args]
         if args and all(isinstance(a, Scalar) for a in args) and name not in ("coalesce",):
             return self._func_scalar(e, args)

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import datetime
 import itertools
+import re
 from decimal import Decimal
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -828,6 +829,8 @@ class Binder:
             if t.is_zoned:
                 from ..utils import tzdb
                 tzdb.check_zone(t.tz)
+            if node.get("try"):
+                return self._try_cast(x, t)
             return self._cast(x, t)
         if k == "case":
             return self._case(node, scope, allow_agg)
@@ -914,6 +917,35 @@ class Binder:
         if src.is_zoned or t.is_zoned:
             return self._cast_zoned(x, t)
         return Cast(x, t)
+
+    def _try_cast(self, x: Expr, t: DataType) -> Expr:
+        """TRY_CAST(x AS t): CAST's value where CAST succeeds in range, NULL elsewhere; never raises at run
+        time. A Func, not a Cast subclass: always nullable, and the generated-kernel paths (exec/expr_jit.py,
+        exec/fused.py) decline it, so it takes the operator path (ops/trycast.py)."""
+        src = x.dtype
+        for side in (src, t):
+            if side.is_nested or side.is_binary or side.kind == "interval":
+                raise NotSupported(f"TRY_CAST({src} AS {t}): {side} is not supported by TRY_CAST")
+        if src.is_string and t.is_zoned:
+            raise NotSupported(f"TRY_CAST({src} AS {t}): timestamp text with a zone is read by CAST only")
+        if src == t:
+            return x
+        if isinstance(x, Lit):
+            return _fold_try_cast(x, t)
+        if src.is_zoned or t.is_zoned or src.kind == "null":
+            return self._cast(x, t)             # cannot fail (or is the PlanError it is for CAST)
+        return Func("try_cast", [x], t)
+
+    def _arrow_cast(self, args: List[Expr]) -> Expr:
+        """arrow_cast(x, 'Type'): CAST to the type spelled as arrow_typeof prints it."""
+        _nargs("arrow_cast", args, 2)
+        if not isinstance(args[1], Lit) or not isinstance(args[1].value, str):
+            raise PlanError("arrow_cast(value, type): the type must be a string constant such as 'Int32'")
+        t = parse_arrow_type_name(args[1].value)
+        if t.is_zoned:
+            from ..utils import tzdb
+            tzdb.check_zone(t.tz)
+        return self._cast(args[0], t)
 
     def _cast_zoned(self, x: Expr, t: DataType) -> Expr:
         """Casts from or to TIMESTAMP WITH TIME ZONE (x is no literal)."""
@@ -1239,6 +1271,8 @@ class Binder:
         if name == "arrow_typeof":
             _nargs(name, args, 1)
             return Lit(arrow_type_name(args[0].dtype), UTF8)
+        if name == "arrow_cast":
+            return self._arrow_cast(args)
         if name in _NESTED_FUNCS:
             return self._nested_func(name, args)
         if name in ("md5", "sha224", "sha256", "sha384", "sha512", "digest"):
@@ -1644,6 +1678,8 @@ class Binder:
         if name == "arrow_typeof":
             _nargs(name, args, 1)
             return Lit(arrow_type_name(args[0].dtype), UTF8)
+        if name == "arrow_cast":
+            return self._arrow_cast(args)
         if name in ("length", "octet_length", "bit_length"):
             _nargs(name, args, 1)
             a = args[0]
@@ -2187,6 +2223,29 @@ def arrow_type_name(t: DataType) -> str:
     return str(t)
 
 
+_ARROW_SCALAR_NAMES = {str(t): t for t in (BOOL, T.INT8, T.INT16, INT32, INT64, T.FLOAT32, FLOAT64, DATE32, UTF8,
+                                             T.BINARY, T.NULL)}
+_ARROW_SCALAR_NAMES["LargeUtf8"] = UTF8
+_ARROW_SCALAR_NAMES["LargeBinary"] = T.BINARY
+_ARROW_DECIMAL = re.compile(r"Decimal128\(\s*(\d+)\s*,\s*(\d+)\s*\)")
+_ARROW_TIMESTAMP = re.compile(r'Timestamp\(\s*(?:Microsecond|us)\s*(?:,\s*(None|Some\("([^"]+)"\)|"([^"]+)"))?\s*\)')
+
+
+def parse_arrow_type_name(name: str) -> DataType:
+    """The inverse of ``arrow_type_name`` for every scalar type it can print; PlanError for anything else."""
+    s = name.strip()
+    if s in _ARROW_SCALAR_NAMES:
+        return _ARROW_SCALAR_NAMES[s]
+    m = _ARROW_DECIMAL.fullmatch(s)
+    if m and 1 <= int(m.group(1)) <= 38 and int(m.group(2)) <= int(m.group(1)):
+        return T.DECIMAL(int(m.group(1)), int(m.group(2)))
+    m = _ARROW_TIMESTAMP.fullmatch(s)
+    if m:
+        tz = m.group(2) or m.group(3)
+        return T.TIMESTAMPTZ(tz) if tz else T.TIMESTAMP
+    raise PlanError(f"arrow_cast: unknown or unsupported type name {name!r} (scalar types as arrow_typeof prints them)")
+
+
 def _like_escape(s: str) -> str:
     return s.replace("\\", "\\\\").replace("%", "\\%").replace("_", "\\_")
 
@@ -2525,6 +2584,34 @@ def _fold_cast(v: Lit, t: DataType) -> Lit:
     return Lit(x, t)
 
 
+def _fits(v, t: DataType) -> bool:
+    """A folded value is inside its type's range (integers by width, decimals by int64 and precision)."""
+    if isinstance(v, float):
+        return True
+    if t.is_integer or t.kind == "date32":
+        bits = 32 if t.kind == "date32" else int(t.kind[3:])
+        return -(1 << (bits - 1)) <= v < (1 << (bits - 1))
+    if t.is_decimal:
+        return -(1 << 63) <= v < (1 << 63) and (t.precision > 18 or abs(v) < 10**t.precision)
+    if t.kind == "timestamp":
+        return -(1 << 63) <= v < (1 << 63)
+    return True
+
+
+def _fold_try_cast(v: Lit, t: DataType) -> Lit:
+    """TRY_CAST of a literal: what ``_fold_cast`` gives where it accepts the value and the result fits t,
+    NULL otherwise. (``_fold_cast`` checks no integer width or decimal precision itself.)"""
+    if TPL.tracking(v):
+        return TPL.derive(lambda a, t=t: _fold_try_cast(a, t), v)
+    if v.value is None:
+        return Lit(None, t)
+    try:
+        out = _fold_cast(v, t)
+    except (PlanError, ExecutionError, ValueError, ArithmeticError, TypeError):
+        return Lit(None, t)
+    return out if out.value is None or _fits(out.value, t) else Lit(None, t)
+
+
 #: CAST(timestamptz AS VARCHAR): YYYY-MM-DDTHH:MM:SS[.ffffff]+HH:MM
 _TSTZ_TEXT = "%Y-%m-%dT%H:%M:%S%#f%:z"
 
@@ -2672,7 +2759,7 @@ def _ast_text(n: dict) -> str:
     if k == "un":
         return ("NOT " if n["s"] == "not" else "-") + _ast_text(n["c"][0])
     if k == "cast":
-        return f"CAST({_ast_text(n['c'][0])} AS {n['type']})"
+        return f"{'TRY_' if n.get('try') else ''}CAST({_ast_text(n['c'][0])} AS {n['type']})"
     if k == "case":
         return "CASE ... END"
     if k == "extract":

@@ -250,6 +250,8 @@ class Func(Expr):
         return Func(self.name, kids, self.dtype, self.options)
 
     def sql(self):
+        if self.name == "try_cast":
+            return f"TRY_CAST({self.args[0].sql()} AS {self.dtype})"
         opt = f"[{','.join(map(str, self.options))}]" if self.options else ""
         return f"{self.name}{opt}({', '.join(a.sql() for a in self.args)})"
 

@@ -56,7 +56,7 @@ DATETIME: Dict[str, str] = {
 }
 SYSTEM: Dict[str, str] = {
     "coalesce": "coalesce(s, 'none')", "ifnull": "ifnull(n, 0)", "nvl": "nvl(n, -1)", "nullif": "nullif(n, 2)",
-    "nvl2": "nvl2(s, 1, 0)", "grouping": "grouping(s)",
+    "nvl2": "nvl2(s, 1, 0)", "grouping": "grouping(s)", "arrow_cast": "arrow_cast(n, 'Int32')",
 }
 AGGREGATE: Dict[str, str] = {
     "count": "count(n)", "sum": "sum(n)", "avg": "avg(f)", "mean": "mean(f)", "min": "min(s)", "max": "max(d)",
