@@ -36,6 +36,15 @@ __device__ inline int64_t load_int(const AggDesc& a, int64_t i) {
   return a.src64 ? ((const int64_t*)a.src)[i] : (int64_t)((const int32_t*)a.src)[i];
 }
 
+// Ordered image of a MIN/MAX f64 input. The aggregates' order is
+// -inf < ... < +inf < NaN with every NaN one value: f64_to_ordered alone puts
+// a NaN whose sign bit is set below -inf (and an all-ones payload on the
+// states' INT64_MAX / INT64_MIN identities), so each NaN takes the image of
+// the canonical quiet NaN, above +inf's and clear of both identities.
+__device__ inline int64_t f64_agg_key(double d) {
+  return d != d ? 0x7ff8000000000000LL : f64_to_ordered(d);
+}
+
 // ---- state update primitives (work on LDS or global pointers alike) -------
 __device__ inline void upd(const AggDesc& a, int64_t i, unsigned long long* lo, long long* hi) {
   switch (a.op) {
@@ -57,10 +66,10 @@ __device__ inline void upd(const AggDesc& a, int64_t i, unsigned long long* lo, 
       atomicMax((long long*)lo, (long long)load_int(a, i));
       break;
     case AGG_MIN_F64:
-      atomicMin((long long*)lo, (long long)f64_to_ordered(((const double*)a.src)[i]));
+      atomicMin((long long*)lo, (long long)f64_agg_key(((const double*)a.src)[i]));
       break;
     case AGG_MAX_F64:
-      atomicMax((long long*)lo, (long long)f64_to_ordered(((const double*)a.src)[i]));
+      atomicMax((long long*)lo, (long long)f64_agg_key(((const double*)a.src)[i]));
       break;
     case AGG_BIT_AND:
       atomicAnd(lo, (unsigned long long)load_int(a, i));
@@ -238,7 +247,7 @@ __device__ inline void row_state(const AggDesc& a, int64_t i, bool live, unsigne
       *lo = (unsigned long long)load_int(a, i);
       break;
     default:
-      *lo = (unsigned long long)f64_to_ordered(((const double*)a.src)[i]);
+      *lo = (unsigned long long)f64_agg_key(((const double*)a.src)[i]);
       break;
   }
 }
@@ -316,7 +325,7 @@ __device__ inline unsigned load_vals8(const AggDesc& a, int64_t r0, int64_t n, u
       for (int j = 0; j < kSortedRows; ++j) {
         double d;
         __builtin_memcpy(&d, &v[j], 8);
-        v[j] = (unsigned long long)f64_to_ordered(d);
+        v[j] = (unsigned long long)f64_agg_key(d);
       }
     }
   } else {
@@ -343,12 +352,17 @@ __global__ __launch_bounds__(kBlock) void agg_sorted_chunk_kernel(const int32_t*
     const int64_t r0 = base + (int64_t)lane * kSortedRows;
     int g[kSortedRows];
     load_gids8(gid, r0, n, g);
-    const bool valid = g[0] >= 0;
+    // rows of this lane's chunk inside the input. A row is live by its index,
+    // not by its id: ids outside [0, groups) form segments like any other
+    // (a negative prefix, a tail past the group count) and are dropped where
+    // a segment is written (merge_global / store_exclusive)
+    const int live = n - r0 >= kSortedRows ? kSortedRows : (n > r0 ? (int)(n - r0) : 0);
+    const bool valid = live > 0;
     int gT = g[0];
     bool multi = false;
 #pragma unroll
     for (int j = 1; j < kSortedRows; ++j) {
-      if (g[j] >= 0) {
+      if (j < live) {
         multi |= g[j] != gT;
         gT = g[j];
       }
@@ -382,7 +396,7 @@ __global__ __launch_bounds__(kBlock) void agg_sorted_chunk_kernel(const int32_t*
       bool in_head = true;
 #pragma unroll
       for (int j = 0; j < kSortedRows; ++j) {
-        if (g[j] < 0) break;
+        if (j >= live) break;
         if (j > 0 && g[j] != g[j - 1]) {
           if (in_head) {
             hlo = lo;
@@ -465,13 +479,15 @@ __device__ inline void wave_fold(const AggDesc& a, unsigned long long& lo, long 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void agg_single_kernel(int64_t n, AggParams p) {
+// gid (may be null: every row counts): with one group, only rows of id 0
+__global__ __launch_bounds__(kBlock) void agg_single_kernel(const int32_t* __restrict__ gid, int64_t n, AggParams p) {
   unsigned long long lo[kMaxAggs];
   long long hi[kMaxAggs];
 #pragma unroll
   for (int k = 0; k < kMaxAggs; ++k)
     if (k < p.nagg) init_state(p.d[k].op, &lo[k], &hi[k]);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (gid && gid[i] != 0) continue;
 #pragma unroll
     for (int k = 0; k < kMaxAggs; ++k) {
       if (k >= p.nagg) break;
@@ -506,12 +522,12 @@ __global__ __launch_bounds__(kBlock) void agg_single_kernel(int64_t n, AggParams
           break;
         }
         case AGG_MIN_F64: {
-          long long v = f64_to_ordered(((const double*)a.src)[i]);
+          long long v = f64_agg_key(((const double*)a.src)[i]);
           if (v < (long long)lo[k]) lo[k] = (unsigned long long)v;
           break;
         }
         case AGG_MAX_F64: {
-          long long v = f64_to_ordered(((const double*)a.src)[i]);
+          long long v = f64_agg_key(((const double*)a.src)[i]);
           if (v > (long long)lo[k]) lo[k] = (unsigned long long)v;
           break;
         }
@@ -605,7 +621,7 @@ __device__ inline bool row_value(const AggDesc& a, int64_t i, unsigned long long
   } else if (a.op == AGG_SUM_F64 || a.op == AGG_MIN_F64 || a.op == AGG_MAX_F64) {
     const double d = ((const double*)a.src)[i];
     if (a.op == AGG_SUM_F64) __builtin_memcpy(v, &d, 8);
-    else *v = (unsigned long long)f64_to_ordered(d);
+    else *v = (unsigned long long)f64_agg_key(d);
   } else {
     *v = a.src64 ? (unsigned long long)((const int64_t*)a.src)[i]
                  : (unsigned long long)(long long)((const int32_t*)a.src)[i];
@@ -1091,7 +1107,7 @@ void agg_update(const int32_t* gid, int64_t n, int ngroups, const AggDesc* descs
   }
   if (ngroups <= 1 || gid == nullptr) {
     // 1024 workgroups: 4 per CU stream the input, 1024 atomics per aggregate
-    hipLaunchKernelGGL(agg_single_kernel, dim3(grid_for(n, kBlock * 4, 1024)), dim3(kBlock), 0, stream, n, p);
+    hipLaunchKernelGGL(agg_single_kernel, dim3(grid_for(n, kBlock * 4, 1024)), dim3(kBlock), 0, stream, gid, n, p);
     check_launch("agg_single", stream);
   } else if (ngroups <= agg_lds_max_groups(nagg)) {
     size_t lds = (size_t)nagg * ngroups * 16;
@@ -1268,9 +1284,9 @@ __device__ inline int64_t part_value(const AggDesc& a, int64_t i) {
     case AGG_MAX_INT:
       return ok ? load_int(a, i) : INT64_MIN;
     case AGG_MIN_F64:
-      return ok ? f64_to_ordered(((const double*)a.src)[i]) : INT64_MAX;
+      return ok ? f64_agg_key(((const double*)a.src)[i]) : INT64_MAX;
     case AGG_MAX_F64:
-      return ok ? f64_to_ordered(((const double*)a.src)[i]) : INT64_MIN;
+      return ok ? f64_agg_key(((const double*)a.src)[i]) : INT64_MIN;
     case AGG_BIT_AND:
       return ok ? load_int(a, i) : -1;
     default:  // OR, XOR

@@ -7,7 +7,11 @@
 //
 // Layout (struct-of-arrays, one HBM line per probe in the common case):
 //   hashed mode: tkeys[cap] int64 (kEmptyKey = empty) + thead[cap] int32,
-//                open addressing with linear probing, cap = pow2 >= 2n;
+//                open addressing with linear probing, cap = pow2 >= 2n. The
+//                key that equals kEmptyKey lives in one reserved slot, index
+//                cap, outside the probed range: every per-slot array of a
+//                hashed table has cap + 1 entries, and tkeys[cap] stays
+//                kEmptyKey, so that slot "holds" the key from the start;
 //   direct mode: when the key domain [kmin, kmin+cap) is dense enough the
 //                key itself is the slot (a perfect hash): no key array, no
 //                probing, one random read per probe row. TPC-H keys are
@@ -39,9 +43,17 @@ __device__ inline bool load_key(const K* keys, const uint8_t* valid, int64_t i, 
   return true;
 }
 
-// Find the slot holding `k` (hashed mode); -1 when absent.
+// First slot of `k`'s probe chain (hashed mode). A key equal to kEmptyKey
+// cannot be told from an empty slot, so it starts (and ends: tkeys[cap] is
+// never claimed and compares equal to it) at the reserved slot past the table.
+__device__ inline int64_t home_slot(int64_t mask, int64_t k) {
+  return k == kEmptyKey ? mask + 1 : (int64_t)(mix64((uint64_t)k) & (uint64_t)mask);
+}
+
+// Find the slot holding `k` (hashed mode); -1 when absent (the reserved slot
+// for k == kEmptyKey: its per-slot entries are empty when no row had the key).
 __device__ inline int64_t find_slot(const int64_t* __restrict__ tkeys, int64_t mask, int64_t k) {
-  int64_t slot = (int64_t)(mix64((uint64_t)k) & (uint64_t)mask);
+  int64_t slot = home_slot(mask, k);
   for (;;) {
     int64_t tk = tkeys[slot];
     if (tk == k) return slot;
@@ -60,7 +72,7 @@ __device__ inline int64_t find_slot(const int64_t* __restrict__ tkeys, int64_t m
 // therefore be a plain (L1-cached) load: hot slots are served per CU instead
 // of queueing on one L2 line.
 __device__ inline int64_t insert_slot(int64_t* __restrict__ tkeys, int64_t mask, int64_t k, bool* existed) {
-  int64_t slot = (int64_t)(mix64((uint64_t)k) & (uint64_t)mask);
+  int64_t slot = home_slot(mask, k);
   for (;;) {
     const int64_t cur = tkeys[slot];
     if (cur == k) { *existed = true; return slot; }
@@ -334,7 +346,7 @@ __global__ __launch_bounds__(kBlock) void groupby_build_kernel(const K* __restri
       bool existed;
       slot = insert_slot(tkeys, mask, k, &existed);
       const int h = (int)(slot & (kRowCache - 1));
-      int cur = cap <= ((int64_t)1 << 31) ? cslot[h] : -2;    // (slots must fit the int32 cache)
+      int cur = cap < ((int64_t)1 << 31) ? cslot[h] : -2;    // (slots, the reserved one included, must fit the int32 cache)
       if (cur == -1) {
         cur = atomicCAS(&cslot[h], -1, (int32_t)slot);
         if (cur == -1) cur = (int32_t)slot;
@@ -651,7 +663,7 @@ __device__ inline void probe_heads(const K* __restrict__ keys, const uint8_t* __
     int64_t slot[kHitBatch], tk[kHitBatch];
 #pragma unroll
     for (int r = 0; r < kHitBatch; ++r) {
-      slot[r] = (int64_t)(mix64((uint64_t)k[r]) & (uint64_t)mask);
+      slot[r] = home_slot(mask, k[r]);
       tk[r] = tkeys[slot[r]];
     }
 #pragma unroll
@@ -1152,7 +1164,8 @@ __global__ __launch_bounds__(kFoldBlock, 8) void probe_stream_kernel(const K* __
 }
 
 // One launch for everything join_build expects initialised: thead = -1,
-// tkeys = kEmptyKey (hashed tables), bits = 0, dups = 0. A segment is an
+// tkeys = kEmptyKey (hashed tables), bits = 0, dups = 0 (cap: entries of
+// thead and tkeys, a hashed table's reserved slot included). A segment is an
 // array of 4-byte words whose fill repeats every 8 bytes (lo, hi): 16-byte
 // stores over its whole chunks, word stores for the up to three words left.
 struct FillSeg {

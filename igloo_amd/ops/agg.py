@@ -3,6 +3,12 @@
 ``grouped_aggregate`` updates up to 8 aggregate states per launch from one
 pass over the group ids. Integer SUMs are exact 128-bit; the result comes
 back as int64 when every group fits, else as an [g, 2] (lo, hi) tensor.
+
+Rows whose group id lies outside [0, ngroups) belong to no group, on every
+path. A group without a (non-NULL) row keeps the identity: 0 for SUM / COUNT,
+I64_MAX / I64_MIN for integer MIN / MAX, +inf / -inf for f64 MIN / MAX, -1 / 0
+/ 0 for AND / OR / XOR. f64 MIN / MAX order -inf < ... < +inf < NaN, a NaN of
+either sign being the one greatest value.
 """
 from __future__ import annotations
 
@@ -202,12 +208,15 @@ def _cpu(gid, ngroups, specs, n) -> List[torch.Tensor]:
         gi = torch.zeros(n, dtype=torch.int64)
     else:
         gi = gid.to(torch.int64)
+    # group ids outside [0, g) are skipped, as every GPU regime skips them
+    inside = (gi >= 0) & (gi < g)
+    inside = None if bool(inside.all().item()) else inside
     outs = []
     for op, vals, valid in specs:
         idx = gi
         v = vals
-        if valid is not None:
-            sel = valid
+        sel = valid if inside is None else (inside if valid is None else valid & inside)
+        if sel is not None:
             idx = gi[sel]
             v = vals[sel] if vals is not None else None
         if op == "count":
@@ -233,9 +242,20 @@ def _cpu(gid, ngroups, specs, n) -> List[torch.Tensor]:
             base = torch.full((g,), init, dtype=torch.int64)
             outs.append(base.scatter_reduce(0, idx, v.to(torch.int64), reduce="amin" if op == "min_int" else "amax"))
         elif op in ("min_f64", "max_f64"):
+            # the order is -inf < ... < +inf < NaN, every NaN one value (as the
+            # GPU's ordered images, csrc/kernels/agg.hip f64_agg_key): MAX is
+            # NaN once a group holds one, MIN only when it holds nothing else
+            # (scatter_reduce alone would propagate NaN through both)
             init = float("inf") if op == "min_f64" else float("-inf")
-            base = torch.full((g,), init, dtype=torch.float64)
-            outs.append(base.scatter_reduce(0, idx, v.to(torch.float64), reduce="amin" if op == "min_f64" else "amax"))
+            v = v.to(torch.float64)
+            nan = v != v
+            num = ~nan
+            res = torch.full((g,), init, dtype=torch.float64).scatter_reduce(
+                0, idx[num], v[num], reduce="amin" if op == "min_f64" else "amax")
+            to_nan = torch.zeros(g, dtype=torch.bool).index_fill_(0, idx[nan], True)
+            if op == "min_f64":
+                to_nan &= ~torch.zeros(g, dtype=torch.bool).index_fill_(0, idx[num], True)
+            outs.append(torch.where(to_nan, torch.full_like(res, float("nan")), res))
         elif op in ("and_int", "or_int", "xor_int"):
             import numpy as np
             ufn = {"and_int": np.bitwise_and, "or_int": np.bitwise_or, "xor_int": np.bitwise_xor}[op]

@@ -213,17 +213,23 @@ class JoinTable:
         span = kmax - self.kmin + 1
         self.direct = self._direct_for(span, n)
         if not self.gpu:
-            k = keys if valid is None else torch.where(valid, keys, torch.full_like(keys, kmax + 1) if kmax < 2**62 else keys)
+            # NULL rows leave before the sort (no key value is free to park
+            # them behind the others: the keys may reach INT64_MAX)
+            rows = None if valid is None else torch.nonzero(valid).reshape(-1)
+            k = keys if rows is None else keys.index_select(0, rows)
             sk, order = torch.sort(k.to(torch.int64), stable=True)
-            if valid is not None:
-                nv = int(valid.sum().item())
-                sk, order = sk[:nv], order[:nv]
+            if rows is not None:
+                order = rows.index_select(0, order)
             self.sorted_keys, self.order = sk, order
             self.unique = bool((sk[1:] != sk[:-1]).all().item()) if sk.numel() > 1 else True
             return
         known_unique = valid is None and key_unique(keys)
         N = launch("join_build")
         self.cap = span if self.direct else _next_pow2(2 * n)
+        # entries of every per-slot array: a hashed table keeps one reserved
+        # slot past its cap probed ones for the key equal to EMPTY_KEY
+        # (csrc/kernels/hashtable.hip home_slot)
+        self.slots = self.cap if self.direct else self.cap + 1
         # Bloom filter for selective probes: ~8 bits per key, at most 4 MB (L2-resident)
         self.bits, self.bmask, self._fold = None, 0, None
         if self.direct and EXACT_BITMAP and span <= EXACT_BITMAP_MAX_SPAN:
@@ -238,13 +244,13 @@ class JoinTable:
         # row ids: int32 below 2^31 build rows, int64 above
         self.rid = torch.int32 if n < INT32_MAX else torch.int64
         self.rid64 = self.rid == torch.int64
-        self.thead = torch.empty(self.cap, dtype=self.rid, device=self.device)
-        self.tkeys = torch.empty(1 if self.direct else self.cap, dtype=torch.int64, device=self.device)
+        self.thead = torch.empty(self.slots, dtype=self.rid, device=self.device)
+        self.tkeys = torch.empty(1 if self.direct else self.slots, dtype=torch.int64, device=self.device)
         dups = torch.empty(1, dtype=torch.int64, device=self.device)
         k64 = keys.dtype == torch.int64
         st = stream(keys)
         # thead = -1, tkeys = EMPTY_KEY (hashed), bits = 0, dups = 0: one launch
-        N.join_table_init(ptr(self.thead), self.rid64, self.cap, 0 if self.direct else ptr(self.tkeys),
+        N.join_table_init(ptr(self.thead), self.rid64, self.slots, 0 if self.direct else ptr(self.tkeys),
                           ptr(self.bits), 0 if self.bits is None else self.bits.numel(), ptr(dups), st)
         N.join_build(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
                      self.kmin, self.direct, ptr(dups), ptr(self.bits), self.bmask, st)
@@ -281,10 +287,10 @@ class JoinTable:
             k64 = keys.dtype == torch.int64
             st = stream(keys)
             n = self.n
-            cnt = torch.zeros(self.cap + 1, dtype=self.rid, device=self.device)
+            cnt = torch.zeros(self.slots + 1, dtype=self.rid, device=self.device)
             launch("join_csr_count").join_csr_count(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(cnt),
                                                     self.rid64, self.cap, self.kmin, self.direct, st)
-            self.cstart = torch.zeros(self.cap + 1, dtype=self.rid, device=self.device)
+            self.cstart = torch.zeros(self.slots + 1, dtype=self.rid, device=self.device)
             torch.cumsum(cnt[:-1], 0, dtype=self.rid, out=self.cstart[1:])
             self.crows = torch.empty(n, dtype=self.rid, device=self.device)
             launch("join_csr_scatter").join_csr_scatter(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(cnt),
@@ -800,7 +806,9 @@ def group_ids_ex(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor, b
 
 
 def _group_table(keys: torch.Tensor, n: int) -> Tuple[int, bool, int]:
-    """(kmin, direct-mapped?, slots) of the group-by table over ``keys``."""
+    """(kmin, direct-mapped?, cap) of the group-by table over ``keys``. A
+    hashed table's per-slot arrays hold ``cap + 1`` entries: the last one is
+    the reserved slot of the key equal to EMPTY_KEY (``_group_slots``)."""
     bnd = key_bound(keys)
     if bnd is not None and (bnd[1] - bnd[0] + 1 <= 2 * n + 65536 or n < BOUND_TRUST_ROWS):
         kmin, kmax = bnd         # a readback-free bound decides: no range readback
@@ -811,6 +819,10 @@ def _group_table(keys: torch.Tensor, n: int) -> Tuple[int, bool, int]:
     span = kmax - kmin + 1
     direct = span <= 2 * n + 65536 and span < 2**31 - 1
     return kmin, direct, span if direct else _next_pow2(2 * n)
+
+
+def _group_slots(direct: bool, cap: int) -> int:
+    return cap if direct else cap + 1
 
 
 def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
@@ -832,17 +844,18 @@ def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
     N = launch("groupby")
     s = stream(keys)
     k64 = keys.dtype == torch.int64
-    trow = torch.full((cap,), INT32_MAX, dtype=torch.int32, device=dev)
+    nslots = _group_slots(direct, cap)
+    trow = torch.full((nslots,), INT32_MAX, dtype=torch.int32, device=dev)
     tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
-             else torch.full((cap,), EMPTY_KEY, dtype=torch.int64, device=dev))
+             else torch.full((nslots,), EMPTY_KEY, dtype=torch.int64, device=dev))
     N.groupby_build(ptr(keys), k64, n, ptr(tkeys), ptr(trow), cap, kmin, direct, s)
-    occ = torch.empty(cap, dtype=torch.bool, device=dev)
-    gid_of_slot = torch.empty(cap, dtype=torch.int32, device=dev)
-    N.groupby_occupied(ptr(trow), cap, ptr(occ), ptr(gid_of_slot), s)
+    occ = torch.empty(nslots, dtype=torch.bool, device=dev)
+    gid_of_slot = torch.empty(nslots, dtype=torch.int32, device=dev)
+    N.groupby_occupied(ptr(trow), nslots, ptr(occ), ptr(gid_of_slot), s)
     slots = mask_to_indices(occ)
     g = slots.numel()
     rep = torch.empty(g, dtype=torch.int32, device=dev)
-    N.groupby_assign(ptr(slots), slots.dtype == torch.int64, g, cap, ptr(trow), ptr(gid_of_slot), ptr(rep), s)
+    N.groupby_assign(ptr(slots), slots.dtype == torch.int64, g, nslots, ptr(trow), ptr(gid_of_slot), ptr(rep), s)
     gid = torch.empty(n, dtype=torch.int32, device=dev)
     N.groupby_lookup(ptr(keys), k64, n, ptr(tkeys), ptr(gid_of_slot), cap, kmin, direct, ptr(gid), s)
     if not direct and g > 1:
@@ -882,13 +895,14 @@ def first_rows_mask(keys: torch.Tensor) -> torch.Tensor:
         return mark
     kmin, direct, cap = _group_table(keys, n)
     s = stream(keys)
-    trow = torch.full((cap,), INT32_MAX, dtype=torch.int32, device=dev)
+    nslots = _group_slots(direct, cap)
+    trow = torch.full((nslots,), INT32_MAX, dtype=torch.int32, device=dev)
     tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
-             else torch.full((cap,), EMPTY_KEY, dtype=torch.int64, device=dev))
+             else torch.full((nslots,), EMPTY_KEY, dtype=torch.int64, device=dev))
     launch("groupby").groupby_build(ptr(keys), keys.dtype == torch.int64, n, ptr(tkeys), ptr(trow), cap, kmin,
                                     direct, s)
     mark = torch.zeros(n, dtype=torch.bool, device=dev)
-    launch("mark_slot_rows").mark_slot_rows(ptr(trow), cap, n, ptr(mark), s)
+    launch("mark_slot_rows").mark_slot_rows(ptr(trow), nslots, n, ptr(mark), s)
     return mark
 
 
