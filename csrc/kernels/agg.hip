@@ -32,10 +32,6 @@ struct AggParams {
 
 __device__ inline bool row_valid(const AggDesc& a, int64_t i) { return !a.valid || a.valid[i]; }
 
-__device__ inline int64_t load_int(const AggDesc& a, int64_t i) {
-  return a.src64 ? ((const int64_t*)a.src)[i] : (int64_t)((const int32_t*)a.src)[i];
-}
-
 // Ordered image of a MIN/MAX f64 input. The aggregates' order is
 // -inf < ... < +inf < NaN with every NaN one value: f64_to_ordered alone puts
 // a NaN whose sign bit is set below -inf (and an all-ones payload on the
@@ -45,100 +41,150 @@ __device__ inline int64_t f64_agg_key(double d) {
   return d != d ? 0x7ff8000000000000LL : f64_to_ordered(d);
 }
 
-// ---- state update primitives (work on LDS or global pointers alike) -------
-__device__ inline void upd(const AggDesc& a, int64_t i, unsigned long long* lo, long long* hi) {
-  switch (a.op) {
-    case AGG_SUM_INT: {
-      int64_t v = load_int(a, i);
-      atomic_add_i128(lo, hi, v);
-      break;
-    }
-    case AGG_SUM_F64:
-      atomicAdd((double*)lo, ((const double*)a.src)[i]);
-      break;
-    case AGG_COUNT:
-      atomicAdd(lo, 1ULL);
-      break;
+// ---- the operators ----------------------------------------------------------
+// Everything a regime knows about an operator is one of these: its identity,
+// the 64-bit image of a row, the plain and the atomic combine of two states.
+__device__ inline bool is_f64_op(int op) { return op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64; }
+
+// the identity's lo word (hi = 0)
+__device__ inline unsigned long long identity(int op) {
+  switch (op) {
     case AGG_MIN_INT:
-      atomicMin((long long*)lo, (long long)load_int(a, i));
-      break;
-    case AGG_MAX_INT:
-      atomicMax((long long*)lo, (long long)load_int(a, i));
-      break;
     case AGG_MIN_F64:
-      atomicMin((long long*)lo, (long long)f64_agg_key(((const double*)a.src)[i]));
-      break;
+      return (unsigned long long)INT64_MAX;
+    case AGG_MAX_INT:
     case AGG_MAX_F64:
-      atomicMax((long long*)lo, (long long)f64_agg_key(((const double*)a.src)[i]));
-      break;
+      return (unsigned long long)INT64_MIN;
     case AGG_BIT_AND:
-      atomicAnd(lo, (unsigned long long)load_int(a, i));
-      break;
-    case AGG_BIT_OR:
-      atomicOr(lo, (unsigned long long)load_int(a, i));
-      break;
-    case AGG_BIT_XOR:
-      atomicXor(lo, (unsigned long long)load_int(a, i));
-      break;
+      return ~0ULL;
+    default:
+      return 0;
   }
 }
 
 __device__ inline void init_state(int op, unsigned long long* lo, long long* hi) {
+  *lo = identity(op);
+  *hi = 0;
+}
+
+// 64-bit payload of row i: an integer sign-extended, the f64 bits for SUM, the
+// ordered image for f64 MIN / MAX, 1 for COUNT (the one place that reads a
+// source value row by row)
+__device__ inline unsigned long long row_image(const AggDesc& a, int64_t i) {
+  if (a.op == AGG_COUNT) return 1;
+  if (is_f64_op(a.op)) {
+    const double d = ((const double*)a.src)[i];
+    if (a.op != AGG_SUM_F64) return (unsigned long long)f64_agg_key(d);
+    unsigned long long bits;
+    __builtin_memcpy(&bits, &d, 8);
+    return bits;
+  }
+  return a.src64 ? (unsigned long long)((const int64_t*)a.src)[i]
+                 : (unsigned long long)(long long)((const int32_t*)a.src)[i];
+}
+
+// (lo, hi) <- (lo, hi) op (olo, ohi); only an integer SUM has a high word.
+// MIN / MAX are selects under cases of their own: as compare-and-store under
+// `default:` they cost agg_single_kernel a wave of occupancy
+__device__ inline void combine(int op, unsigned long long& lo, long long& hi, unsigned long long olo, long long ohi) {
   switch (op) {
+    case AGG_SUM_INT: {
+      const unsigned long long s = lo + olo;
+      hi = hi + ohi + (s < lo ? 1 : 0);
+      lo = s;
+      break;
+    }
+    case AGG_SUM_F64: {
+      double x, y;
+      __builtin_memcpy(&x, &lo, 8);
+      __builtin_memcpy(&y, &olo, 8);
+      x += y;
+      __builtin_memcpy(&lo, &x, 8);
+      break;
+    }
+    case AGG_COUNT:
+      lo += olo;
+      break;
     case AGG_MIN_INT:
     case AGG_MIN_F64:
-      *(long long*)lo = INT64_MAX;
+      lo = (long long)olo < (long long)lo ? olo : lo;
       break;
     case AGG_MAX_INT:
     case AGG_MAX_F64:
-      *(long long*)lo = INT64_MIN;
+      lo = (long long)olo > (long long)lo ? olo : lo;
       break;
     case AGG_BIT_AND:
-      *lo = ~0ULL;
+      lo &= olo;
       break;
-    default:
-      *lo = 0;
+    case AGG_BIT_OR:
+      lo |= olo;
+      break;
+    case AGG_BIT_XOR:
+      lo ^= olo;
+      break;
   }
-  *hi = 0;
+}
+
+// the sign extension of a row image: an integer SUM's high word
+__device__ inline long long image_hi(int op, unsigned long long x) {
+  return op == AGG_SUM_INT && (long long)x < 0 ? -1LL : 0LL;
+}
+
+// combine with a row image
+__device__ inline void fold(int op, unsigned long long& lo, long long& hi, unsigned long long x) {
+  combine(op, lo, hi, x, image_hi(op, x));
+}
+
+// combine into an LDS or global state (hi == nullptr: a narrow integer SUM)
+__device__ inline void atomic_combine(int op, unsigned long long* lo, long long* hi, unsigned long long x,
+                                      long long xhi) {
+  switch (op) {
+    case AGG_SUM_INT:
+      atomic_add_i128_parts(lo, hi, x, xhi);
+      break;
+    case AGG_SUM_F64: {
+      double d;
+      __builtin_memcpy(&d, &x, 8);
+      atomicAdd((double*)lo, d);
+      break;
+    }
+    case AGG_COUNT:
+      atomicAdd(lo, x);
+      break;
+    case AGG_MIN_INT:
+    case AGG_MIN_F64:
+      atomicMin((long long*)lo, (long long)x);
+      break;
+    case AGG_MAX_INT:
+    case AGG_MAX_F64:
+      atomicMax((long long*)lo, (long long)x);
+      break;
+    case AGG_BIT_AND:
+      atomicAnd(lo, x);
+      break;
+    case AGG_BIT_OR:
+      atomicOr(lo, x);
+      break;
+    case AGG_BIT_XOR:
+      atomicXor(lo, x);
+      break;
+  }
+}
+
+// row i into an LDS or global state
+__device__ inline void upd(const AggDesc& a, int64_t i, unsigned long long* lo, long long* hi) {
+  const unsigned long long x = row_image(a, i);
+  atomic_combine(a.op, lo, hi, x, image_hi(a.op, x));
 }
 
 // merge an LDS/register state into the global output (a group id past the
 // state arrays -- a replayed group count below the real one -- is dropped;
-// the end-of-query check re-executes the query)
+// the end-of-query check re-executes the query). An identity state is skipped:
+// it would change nothing and cost a memory-side request
 __device__ inline void merge_global(const AggDesc& a, int64_t g, unsigned long long lo, long long hi) {
   if (a.groups && (uint64_t)g >= (uint64_t)a.groups) return;
-  unsigned long long* dlo = (unsigned long long*)a.dst + g;
-  switch (a.op) {
-    case AGG_SUM_INT:
-      if (lo != 0 || hi != 0) atomic_add_i128_parts(dlo, a.dst2 ? (long long*)a.dst2 + g : nullptr, lo, hi);
-      break;
-    case AGG_SUM_F64: {
-      double d;
-      __builtin_memcpy(&d, &lo, 8);
-      if (d != 0.0) atomicAdd((double*)dlo, d);
-      break;
-    }
-    case AGG_COUNT:
-      if (lo) atomicAdd(dlo, lo);
-      break;
-    case AGG_MIN_INT:
-    case AGG_MIN_F64:
-      if ((long long)lo != INT64_MAX) atomicMin((long long*)dlo, (long long)lo);
-      break;
-    case AGG_MAX_INT:
-    case AGG_MAX_F64:
-      if ((long long)lo != INT64_MIN) atomicMax((long long*)dlo, (long long)lo);
-      break;
-    case AGG_BIT_AND:
-      if (lo != ~0ULL) atomicAnd(dlo, lo);
-      break;
-    case AGG_BIT_OR:
-      if (lo) atomicOr(dlo, lo);
-      break;
-    case AGG_BIT_XOR:
-      if (lo) atomicXor(dlo, lo);
-      break;
-  }
+  if (lo == identity(a.op) && hi == 0) return;
+  atomic_combine(a.op, (unsigned long long*)a.dst + g, a.dst2 ? (long long*)a.dst2 + g : nullptr, lo, hi);
 }
 
 // ---------------------------------------------------------------- regimes
@@ -185,73 +231,6 @@ __global__ __launch_bounds__(kBlock) void agg_lds_kernel(const int32_t* __restri
 // that touches either edge of the 64-row tile may continue in a neighbouring
 // tile and merges atomically; interior segments belong to this wave alone and
 // are stored without atomics.
-__device__ inline void seg_combine(int op, unsigned long long* lo, long long* hi, unsigned long long olo, long long ohi) {
-  switch (op) {
-    case AGG_SUM_INT: {
-      unsigned long long s = *lo + olo;
-      *hi = *hi + ohi + (s < *lo ? 1 : 0);
-      *lo = s;
-      break;
-    }
-    case AGG_SUM_F64: {
-      double x, y;
-      __builtin_memcpy(&x, lo, 8);
-      __builtin_memcpy(&y, &olo, 8);
-      x += y;
-      __builtin_memcpy(lo, &x, 8);
-      break;
-    }
-    case AGG_COUNT:
-      *lo += olo;
-      break;
-    case AGG_MIN_INT:
-    case AGG_MIN_F64:
-      if ((long long)olo < (long long)*lo) *lo = olo;
-      break;
-    case AGG_BIT_AND:
-      *lo &= olo;
-      break;
-    case AGG_BIT_OR:
-      *lo |= olo;
-      break;
-    case AGG_BIT_XOR:
-      *lo ^= olo;
-      break;
-    default:
-      if ((long long)olo > (long long)*lo) *lo = olo;
-      break;
-  }
-}
-
-__device__ inline void row_state(const AggDesc& a, int64_t i, bool live, unsigned long long* lo, long long* hi) {
-  init_state(a.op, lo, hi);
-  if (!live || !row_valid(a, i)) return;
-  switch (a.op) {
-    case AGG_SUM_INT: {
-      const int64_t v = load_int(a, i);
-      *lo = (unsigned long long)v;
-      *hi = v < 0 ? -1 : 0;
-      break;
-    }
-    case AGG_SUM_F64:
-      __builtin_memcpy(lo, &((const double*)a.src)[i], 8);
-      break;
-    case AGG_COUNT:
-      *lo = 1;
-      break;
-    case AGG_MIN_INT:
-    case AGG_MAX_INT:
-    case AGG_BIT_AND:
-    case AGG_BIT_OR:
-    case AGG_BIT_XOR:
-      *lo = (unsigned long long)load_int(a, i);
-      break;
-    default:
-      *lo = (unsigned long long)f64_agg_key(((const double*)a.src)[i]);
-      break;
-  }
-}
-
 __device__ inline void store_exclusive(const AggDesc& a, int64_t g, unsigned long long lo, long long hi) {
   if (a.groups && (uint64_t)g >= (uint64_t)a.groups) return;   // see merge_global
   ((unsigned long long*)a.dst)[g] = lo;
@@ -284,7 +263,10 @@ __device__ inline void load_gids8(const int32_t* gid, int64_t r0, int64_t n, int
   }
 }
 
-// raw 64-bit row payloads (int sign-extended / f64 bits / 1 for COUNT) and validity bits
+// the row images of a lane's chunk and their validity bits. (The row-by-row
+// tail of a partial or unaligned chunk stands in either width's branch: one
+// shared tail after them cost agg_sorted_chunk_kernel 14 VGPRs and two waves
+// of occupancy.)
 __device__ inline unsigned load_vals8(const AggDesc& a, int64_t r0, int64_t n, unsigned long long v[kSortedRows]) {
   const bool full = r0 + kSortedRows <= n;
   unsigned ok = 0;
@@ -306,8 +288,7 @@ __device__ inline unsigned load_vals8(const AggDesc& a, int64_t r0, int64_t n, u
     for (int j = 0; j < kSortedRows; ++j) v[j] = 1;
     return ok;
   }
-  const bool wide = a.op == AGG_SUM_F64 || a.op == AGG_MIN_F64 || a.op == AGG_MAX_F64 || a.src64;
-  if (wide) {
+  if (is_f64_op(a.op) || a.src64) {
     const unsigned long long* src = (const unsigned long long*)a.src + r0;
     if (full && ((uintptr_t)src & 15) == 0) {
 #pragma unroll
@@ -316,17 +297,17 @@ __device__ inline unsigned load_vals8(const AggDesc& a, int64_t r0, int64_t n, u
         v[j] = x.x;
         v[j + 1] = x.y;
       }
+      if (a.op == AGG_MIN_F64 || a.op == AGG_MAX_F64) {
+#pragma unroll
+        for (int j = 0; j < kSortedRows; ++j) {
+          double d;
+          __builtin_memcpy(&d, &v[j], 8);
+          v[j] = (unsigned long long)f64_agg_key(d);
+        }
+      }
     } else {
 #pragma unroll
-      for (int j = 0; j < kSortedRows; ++j) v[j] = r0 + j < n ? src[j] : 0;
-    }
-    if (a.op == AGG_MIN_F64 || a.op == AGG_MAX_F64) {
-#pragma unroll
-      for (int j = 0; j < kSortedRows; ++j) {
-        double d;
-        __builtin_memcpy(&d, &v[j], 8);
-        v[j] = (unsigned long long)f64_agg_key(d);
-      }
+      for (int j = 0; j < kSortedRows; ++j) v[j] = r0 + j < n ? row_image(a, r0 + j) : 0;
     }
   } else {
     const int32_t* src = (const int32_t*)a.src + r0;
@@ -336,7 +317,7 @@ __device__ inline unsigned load_vals8(const AggDesc& a, int64_t r0, int64_t n, u
       v[4] = (long long)y.x; v[5] = (long long)y.y; v[6] = (long long)y.z; v[7] = (long long)y.w;
     } else {
 #pragma unroll
-      for (int j = 0; j < kSortedRows; ++j) v[j] = r0 + j < n ? (unsigned long long)(long long)src[j] : 0;
+      for (int j = 0; j < kSortedRows; ++j) v[j] = r0 + j < n ? row_image(a, r0 + j) : 0;
     }
   }
   return ok;
@@ -407,20 +388,19 @@ __global__ __launch_bounds__(kBlock) void agg_sorted_chunk_kernel(const int32_t*
           }
           init_state(a.op, &lo, &hi);
         }
-        if (ok & (1u << j))
-          seg_combine(a.op, &lo, &hi, v[j], a.op == AGG_SUM_INT && (long long)v[j] < 0 ? -1LL : 0LL);
+        if (ok & (1u << j)) fold(a.op, lo, hi, v[j]);
       }
       // segmented inclusive scan of the tails across lanes
 #pragma unroll
       for (int s = 0; s < 6; ++s) {
         const unsigned long long olo = __shfl_up(lo, 1 << s, kWave);
         const long long ohi = __shfl_up(hi, 1 << s, kWave);
-        if (lane >= (1 << s) && og[s] == gT) seg_combine(a.op, &lo, &hi, olo, ohi);
+        if (lane >= (1 << s) && og[s] == gT) combine(a.op, lo, hi, olo, ohi);
       }
       const unsigned long long clo = __shfl_up(lo, 1, kWave);
       const long long chi = __shfl_up(hi, 1, kWave);
       if (valid && multi) {
-        if (has_carry) seg_combine(a.op, &hlo, &hhi, clo, chi);
+        if (has_carry) combine(a.op, hlo, hhi, clo, chi);
         if (head_atomic) merge_global(a, gH, hlo, hhi);
         else store_exclusive(a, gH, hlo, hhi);
       }
@@ -440,42 +420,7 @@ __device__ inline void wave_fold(const AggDesc& a, unsigned long long& lo, long 
   for (int off = kWave / 2; off > 0; off >>= 1) {
     unsigned long long olo = __shfl_xor(lo, off, kWave);
     long long ohi = __shfl_xor(hi, off, kWave);
-    switch (a.op) {
-      case AGG_SUM_INT: {
-        unsigned long long s = lo + olo;
-        hi = hi + ohi + (s < lo ? 1 : 0);
-        lo = s;
-        break;
-      }
-      case AGG_SUM_F64: {
-        double x, y;
-        __builtin_memcpy(&x, &lo, 8);
-        __builtin_memcpy(&y, &olo, 8);
-        x += y;
-        __builtin_memcpy(&lo, &x, 8);
-        break;
-      }
-      case AGG_COUNT:
-        lo += olo;
-        break;
-      case AGG_MIN_INT:
-      case AGG_MIN_F64:
-        lo = (long long)olo < (long long)lo ? olo : lo;
-        break;
-      case AGG_MAX_INT:
-      case AGG_MAX_F64:
-        lo = (long long)olo > (long long)lo ? olo : lo;
-        break;
-      case AGG_BIT_AND:
-        lo &= olo;
-        break;
-      case AGG_BIT_OR:
-        lo |= olo;
-        break;
-      case AGG_BIT_XOR:
-        lo ^= olo;
-        break;
-    }
+    combine(a.op, lo, hi, olo, ohi);
   }
 }
 
@@ -492,55 +437,7 @@ __global__ __launch_bounds__(kBlock) void agg_single_kernel(const int32_t* __res
     for (int k = 0; k < kMaxAggs; ++k) {
       if (k >= p.nagg) break;
       const AggDesc& a = p.d[k];
-      if (!row_valid(a, i)) continue;
-      switch (a.op) {
-        case AGG_SUM_INT: {
-          int64_t v = load_int(a, i);
-          unsigned long long s = lo[k] + (unsigned long long)v;
-          hi[k] += (v < 0 ? -1 : 0) + (s < lo[k] ? 1 : 0);
-          lo[k] = s;
-          break;
-        }
-        case AGG_SUM_F64: {
-          double x;
-          __builtin_memcpy(&x, &lo[k], 8);
-          x += ((const double*)a.src)[i];
-          __builtin_memcpy(&lo[k], &x, 8);
-          break;
-        }
-        case AGG_COUNT:
-          lo[k] += 1;
-          break;
-        case AGG_MIN_INT: {
-          long long v = load_int(a, i);
-          if (v < (long long)lo[k]) lo[k] = (unsigned long long)v;
-          break;
-        }
-        case AGG_MAX_INT: {
-          long long v = load_int(a, i);
-          if (v > (long long)lo[k]) lo[k] = (unsigned long long)v;
-          break;
-        }
-        case AGG_MIN_F64: {
-          long long v = f64_agg_key(((const double*)a.src)[i]);
-          if (v < (long long)lo[k]) lo[k] = (unsigned long long)v;
-          break;
-        }
-        case AGG_MAX_F64: {
-          long long v = f64_agg_key(((const double*)a.src)[i]);
-          if (v > (long long)lo[k]) lo[k] = (unsigned long long)v;
-          break;
-        }
-        case AGG_BIT_AND:
-          lo[k] &= (unsigned long long)load_int(a, i);
-          break;
-        case AGG_BIT_OR:
-          lo[k] |= (unsigned long long)load_int(a, i);
-          break;
-        case AGG_BIT_XOR:
-          lo[k] ^= (unsigned long long)load_int(a, i);
-          break;
-      }
+      if (row_valid(a, i)) fold(a.op, lo[k], hi[k], row_image(a, i));
     }
   }
   __shared__ unsigned long long blo[kMaxAggs][kWavesPerBlock];
@@ -560,7 +457,7 @@ __global__ __launch_bounds__(kBlock) void agg_single_kernel(const int32_t* __res
     const int k = threadIdx.x;
     unsigned long long l = blo[k][0];
     long long h = bhi[k][0];
-    for (int v = 1; v < kWavesPerBlock; ++v) seg_combine(p.d[k].op, &l, &h, blo[k][v], bhi[k][v]);
+    for (int v = 1; v < kWavesPerBlock; ++v) combine(p.d[k].op, l, h, blo[k][v], bhi[k][v]);
     merge_global(p.d[k], 0, l, h);
   }
 }
@@ -592,7 +489,7 @@ struct HavingParams {
 __device__ inline bool having_ok(const HavingParams& p, unsigned long long lo, long long hi) {
   const int op = p.d[p.hagg].op;
   int c;
-  if (op == AGG_SUM_F64 || op == AGG_MIN_F64 || op == AGG_MAX_F64) {
+  if (is_f64_op(op)) {
     double x;
     if (op == AGG_SUM_F64) __builtin_memcpy(&x, &lo, 8);
     else x = ordered_to_f64((long long)lo);
@@ -611,26 +508,6 @@ __device__ inline bool having_ok(const HavingParams& p, unsigned long long lo, l
     case 4: return c > 0;
     default: return c >= 0;
   }
-}
-
-// one row of aggregate a from global memory (overhang rows)
-__device__ inline bool row_value(const AggDesc& a, int64_t i, unsigned long long* v) {
-  if (a.valid && !a.valid[i]) return false;
-  if (a.op == AGG_COUNT) {
-    *v = 1;
-  } else if (a.op == AGG_SUM_F64 || a.op == AGG_MIN_F64 || a.op == AGG_MAX_F64) {
-    const double d = ((const double*)a.src)[i];
-    if (a.op == AGG_SUM_F64) __builtin_memcpy(v, &d, 8);
-    else *v = (unsigned long long)f64_agg_key(d);
-  } else {
-    *v = a.src64 ? (unsigned long long)((const int64_t*)a.src)[i]
-                 : (unsigned long long)(long long)((const int32_t*)a.src)[i];
-  }
-  return true;
-}
-
-__device__ inline void fold(int op, unsigned long long* lo, long long* hi, unsigned long long x) {
-  seg_combine(op, lo, hi, x, op == AGG_SUM_INT && (long long)x < 0 ? -1LL : 0LL);
 }
 
 // The runs starting among a lane's 8 rows, folded for ONE aggregate: emit(j,
@@ -663,7 +540,7 @@ __device__ inline void fold_runs(const AggDesc& a, const K* __restrict__ keys, i
       open = j;
       init_state(a.op, &lo, &hi);
     }
-    if (open >= 0 && ((ok >> j) & 1u)) fold(a.op, &lo, &hi, v[j]);
+    if (open >= 0 && ((ok >> j) & 1u)) fold(a.op, lo, hi, v[j]);
   }
   if (open < 0) return;
   const K key = k[open];
@@ -675,7 +552,7 @@ __device__ inline void fold_runs(const AggDesc& a, const K* __restrict__ keys, i
     const int c = nst ? __builtin_ctz(nst) : kSortedRows;
 #pragma unroll
     for (int j = 0; j < kSortedRows; ++j)
-      if (j < c && j < live && ((nok >> j) & 1u)) fold(a.op, &lo, &hi, nv[j]);
+      if (j < c && j < live && ((nok >> j) & 1u)) fold(a.op, lo, hi, nv[j]);
     more = c == kSortedRows && live == kSortedRows;
     r += kSortedRows;
     more = more && r < n;
@@ -688,7 +565,8 @@ __device__ inline void fold_runs(const AggDesc& a, const K* __restrict__ keys, i
     for (int q = 0; q < 4; ++q) {
       const bool in = r + q < n;
       kk[q] = in ? keys[r + q] : key;
-      xv[q] = in && row_value(a, r + q, &x[q]);
+      xv[q] = in && row_valid(a, r + q);
+      x[q] = xv[q] ? row_image(a, r + q) : 0;   // (overhang rows, from global memory)
       if (!in) kk[q] = (K)(key + 1);   // past the end: the run stops there
     }
 #pragma unroll
@@ -698,7 +576,7 @@ __device__ inline void fold_runs(const AggDesc& a, const K* __restrict__ keys, i
         more = false;
         break;
       }
-      if (xv[q]) fold(a.op, &lo, &hi, x[q]);
+      if (xv[q]) fold(a.op, lo, hi, x[q]);
     }
     r += 4;
     if (more && r - (r0 + open) >= kHavingMaxRun) {
@@ -1055,37 +933,26 @@ void sorted_having(const void* keys, bool key64, int64_t n, const AggDesc* descs
       throw std::runtime_error("sorted_having: int16 / int8 values need the streaming kernel");
   if (streaming) {
     const int vb = vagg < 0 ? 0 : descs[vagg].src64 == 0 ? 4 : descs[vagg].src64 == 2 ? 2 : 1;
-    const void* fns[2][4] = {{(const void*)sorted_having_scan_kernel<int32_t, 0>,
-                              (const void*)sorted_having_scan_kernel<int32_t, 1>,
-                              (const void*)sorted_having_scan_kernel<int32_t, 2>,
-                              (const void*)sorted_having_scan_kernel<int32_t, 4>},
-                             {(const void*)sorted_having_scan_kernel<int64_t, 0>,
-                              (const void*)sorted_having_scan_kernel<int64_t, 1>,
-                              (const void*)sorted_having_scan_kernel<int64_t, 2>,
-                              (const void*)sorted_having_scan_kernel<int64_t, 4>}};
-    const int vi = vb == 0 ? 0 : vb == 1 ? 1 : vb == 2 ? 2 : 3;
-    const void* fn = fns[key64 ? 1 : 0][vi];
-    // one resident round of waves (each owns one span): a second, partial
-    // round would double the kernel's time
-    static int resident[2][4] = {};
-    int& res = resident[key64 ? 1 : 0][vi];
-    if (!res) {
-      int dev = 0, cus = 0, per_cu = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, 0);
-      res = std::max(1, cus * std::max(1, per_cu));
-    }
-    const int64_t tiles = (n + kScanTile - 1) / kScanTile;
-    const int64_t blocks = std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock, res);
-    const int64_t waves = blocks * kWavesPerBlock;
-    const int64_t span = (tiles + waves - 1) / waves * kScanTile;
-    const dim3 g((unsigned)((((n + span - 1) / span) + kWavesPerBlock - 1) / kWavesPerBlock)), b(kBlock);
-    int64_t nn = n, sp = span, cp = cap;
-    int va = vagg;
-    void* args[] = {(void*)&keys, &nn, &sp, &p, &va, &rep, &cp, &counter};
-    (void)hipLaunchKernel(fn, g, b, args, 0, stream);
-    check_launch("sorted_having_scan", stream);
+    dispatch(wide{key64}, value_bytes{vb}, [&](auto k, auto v) {
+      using K = type_of<decltype(k)>;
+      const auto kernel = sorted_having_scan_kernel<K, v.value>;
+      // one resident round of waves (each owns one span): a second, partial
+      // round would double the kernel's time
+      static int resident = 0;   // (of this instantiation)
+      if (!resident) {
+        int dev = 0, cus = 0, per_cu = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0);
+        resident = std::max(1, cus * std::max(1, per_cu));
+      }
+      const int64_t tiles = (n + kScanTile - 1) / kScanTile;
+      const int64_t blocks = std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock, resident);
+      const int64_t waves = blocks * kWavesPerBlock;
+      const int64_t span = (tiles + waves - 1) / waves * kScanTile;
+      const dim3 g((unsigned)((((n + span - 1) / span) + kWavesPerBlock - 1) / kWavesPerBlock)), b(kBlock);
+      launch("sorted_having_scan", kernel, g, b, 0, stream, as<K>(keys), n, span, p, vagg, rep, cap, counter);
+    });
     return;
   }
   const dim3 g(grid_for(n, kBlock * kSortedRows, 32768)), b(kBlock);
@@ -1107,21 +974,17 @@ void agg_update(const int32_t* gid, int64_t n, int ngroups, const AggDesc* descs
   }
   if (ngroups <= 1 || gid == nullptr) {
     // 1024 workgroups: 4 per CU stream the input, 1024 atomics per aggregate
-    hipLaunchKernelGGL(agg_single_kernel, dim3(grid_for(n, kBlock * 4, 1024)), dim3(kBlock), 0, stream, gid, n, p);
-    check_launch("agg_single", stream);
+    launch("agg_single", agg_single_kernel, dim3(grid_for(n, kBlock * 4, 1024)), dim3(kBlock), 0, stream, gid, n, p);
   } else if (ngroups <= agg_lds_max_groups(nagg)) {
     size_t lds = (size_t)nagg * ngroups * 16;
     // fewer workgroups when the per-workgroup flush is large
     int64_t maxg = ngroups <= 64 ? 8192 : 2048;
-    hipLaunchKernelGGL(agg_lds_kernel, dim3(grid_for(n, kBlock * 8, maxg)), dim3(kBlock), lds, stream, gid, n, ngroups, p);
-    check_launch("agg_lds", stream);
+    launch("agg_lds", agg_lds_kernel, dim3(grid_for(n, kBlock * 8, maxg)), dim3(kBlock), lds, stream, gid, n, ngroups, p);
   } else if (sorted_gids) {
-    hipLaunchKernelGGL(agg_sorted_chunk_kernel, dim3(grid_for(n, kBlock * kSortedRows, 32768)), dim3(kBlock), 0, stream,
-                       gid, n, p);
-    check_launch("agg_sorted_chunk", stream);
+    launch("agg_sorted_chunk", agg_sorted_chunk_kernel, dim3(grid_for(n, kBlock * kSortedRows, 32768)), dim3(kBlock), 0,
+           stream, gid, n, p);
   } else {
-    hipLaunchKernelGGL(agg_global_kernel, dim3(grid_for(n, kBlock, 32768)), dim3(kBlock), 0, stream, gid, n, p);
-    check_launch("agg_global", stream);
+    launch("agg_global", agg_global_kernel, dim3(grid_for(n, kBlock, 32768)), dim3(kBlock), 0, stream, gid, n, p);
   }
 }
 
@@ -1266,32 +1129,9 @@ struct PartParams {
   int64_t* vals[kMaxAggs];  // scattered inputs per aggregate (null: COUNT(*), 1 per row)
 };
 
+// what a row scatters for aggregate a: its image, the identity for a NULL
 __device__ inline int64_t part_value(const AggDesc& a, int64_t i) {
-  const bool ok = row_valid(a, i);
-  switch (a.op) {
-    case AGG_SUM_INT:
-      return ok ? load_int(a, i) : 0;
-    case AGG_SUM_F64: {
-      const double d = ok ? ((const double*)a.src)[i] : 0.0;
-      int64_t r;
-      __builtin_memcpy(&r, &d, 8);
-      return r;
-    }
-    case AGG_COUNT:
-      return ok ? 1 : 0;
-    case AGG_MIN_INT:
-      return ok ? load_int(a, i) : INT64_MAX;
-    case AGG_MAX_INT:
-      return ok ? load_int(a, i) : INT64_MIN;
-    case AGG_MIN_F64:
-      return ok ? f64_agg_key(((const double*)a.src)[i]) : INT64_MAX;
-    case AGG_MAX_F64:
-      return ok ? f64_agg_key(((const double*)a.src)[i]) : INT64_MIN;
-    case AGG_BIT_AND:
-      return ok ? load_int(a, i) : -1;
-    default:  // OR, XOR
-      return ok ? load_int(a, i) : 0;
-  }
+  return (int64_t)(row_valid(a, i) ? row_image(a, i) : identity(a.op));
 }
 
 __global__ __launch_bounds__(kBlock) void aggp_count_kernel(const int32_t* __restrict__ gid, int64_t n, int64_t groups,
@@ -1329,8 +1169,6 @@ __global__ __launch_bounds__(kBlock) void aggp_scatter_kernel(const int32_t* __r
   }
 }
 
-__device__ inline void part_init(int op, unsigned long long* lo, long long* hi) { init_state(op, lo, hi); }
-
 __global__ __launch_bounds__(kPartBlock2) void aggp_bucket_kernel(const uint16_t* __restrict__ pg,
                                                                  const int64_t* __restrict__ off,
                                                                  const int64_t* __restrict__ total, int nblk,
@@ -1339,7 +1177,7 @@ __global__ __launch_bounds__(kPartBlock2) void aggp_bucket_kernel(const uint16_t
   const int B = 1 << bits;
   unsigned long long* slo = st;
   long long* shi = (long long*)(st + (size_t)p.nagg * B);
-  for (int idx = threadIdx.x; idx < p.nagg * B; idx += blockDim.x) part_init(p.d[idx >> bits].op, &slo[idx], &shi[idx]);
+  for (int idx = threadIdx.x; idx < p.nagg * B; idx += blockDim.x) init_state(p.d[idx >> bits].op, &slo[idx], &shi[idx]);
   __syncthreads();
   // `slices` workgroups share a bucket when the buckets are few (each takes
   // a contiguous slice of its rows and merges with atomics)
@@ -1355,114 +1193,39 @@ __global__ __launch_bounds__(kPartBlock2) void aggp_bucket_kernel(const uint16_t
       const AggDesc& a = p.d[k];
       const int idx = (k << bits) + g;
       const int64_t v = p.vals[k] ? p.vals[k][i] : 1;
-      switch (a.op) {
-        case AGG_SUM_INT:
-          if (a.dst2) {
-            atomicAdd(&slo[idx], (unsigned long long)(uint32_t)v);
-            atomicAdd((unsigned long long*)&shi[idx], (unsigned long long)(v >> 32));
-          } else {
-            atomicAdd(&slo[idx], (unsigned long long)v);
-          }
-          break;
-        case AGG_SUM_F64: {
-          double d;
-          __builtin_memcpy(&d, &v, 8);
-          atomicAdd((double*)&slo[idx], d);
-          break;
-        }
-        case AGG_COUNT:
-          atomicAdd(&slo[idx], (unsigned long long)v);
-          break;
-        case AGG_MIN_INT:
-        case AGG_MIN_F64:
-          atomicMin((long long*)&slo[idx], (long long)v);
-          break;
-        case AGG_MAX_INT:
-        case AGG_MAX_F64:
-          atomicMax((long long*)&slo[idx], (long long)v);
-          break;
-        case AGG_BIT_AND:
-          atomicAnd(&slo[idx], (unsigned long long)v);
-          break;
-        case AGG_BIT_OR:
-          atomicOr(&slo[idx], (unsigned long long)v);
-          break;
-        case AGG_BIT_XOR:
-          atomicXor(&slo[idx], (unsigned long long)v);
-          break;
+      if (a.op == AGG_SUM_INT && a.dst2) {
+        // the 128-bit SUM as a 32 / 32-bit split: two no-return adds
+        atomicAdd(&slo[idx], (unsigned long long)(uint32_t)v);
+        atomicAdd((unsigned long long*)&shi[idx], (unsigned long long)(v >> 32));
+      } else {
+        atomic_combine(a.op, &slo[idx], nullptr, (unsigned long long)v, 0);
       }
     }
   }
   __syncthreads();
-  // merge: this bucket's groups belong to this workgroup alone (plain stores)
+  // merge: this bucket's groups belong to this workgroup alone (plain stores),
+  // unless it shares the bucket with other slices
   const int64_t g0 = (int64_t)b << bits;
-  if (slices > 1) {
-    for (int idx = threadIdx.x; idx < p.nagg * B; idx += blockDim.x) {
-      const int k = idx >> bits;
-      const int64_t g = g0 + (idx & (B - 1));
-      if (g >= groups) continue;
-      const AggDesc& a = p.d[k];
-      unsigned long long x = slo[idx];
-      long long h = 0;
-      if (a.op == AGG_SUM_INT && a.dst2) {
-        const __int128 t = ((__int128)shi[idx] << 32) + (__int128)x;
-        x = (unsigned long long)t;
-        h = (long long)(t >> 64);
-      }
-      merge_global(a, g, x, h);   // (identity states are skipped)
-    }
-    return;
-  }
   for (int idx = threadIdx.x; idx < p.nagg * B; idx += blockDim.x) {
-    const int k = idx >> bits;
     const int64_t g = g0 + (idx & (B - 1));
     if (g >= groups) continue;
-    const AggDesc& a = p.d[k];
-    unsigned long long* d = (unsigned long long*)a.dst + g;
-    const unsigned long long x = slo[idx];
-    switch (a.op) {
-      case AGG_SUM_INT:
-        if (a.dst2) {
-          long long* d2 = (long long*)a.dst2 + g;
-          // total = shi * 2^32 + slo (slo < 2^63, |shi| < 2^62): exact in 128 bits
-          const __int128 t = ((__int128)shi[idx] << 32) + (__int128)x;
-          const __int128 c = (((__int128)*d2) << 64) + (__int128)*d;
-          const __int128 r = c + t;
-          *d = (unsigned long long)r;
-          *d2 = (long long)(r >> 64);
-        } else {
-          *d += x;
-        }
-        break;
-      case AGG_SUM_F64: {
-        double u, w;
-        __builtin_memcpy(&u, d, 8);
-        __builtin_memcpy(&w, &x, 8);
-        u += w;
-        __builtin_memcpy(d, &u, 8);
-        break;
-      }
-      case AGG_COUNT:
-        *d += x;
-        break;
-      case AGG_MIN_INT:
-      case AGG_MIN_F64:
-        if ((long long)x < (long long)*d) *d = x;
-        break;
-      case AGG_MAX_INT:
-      case AGG_MAX_F64:
-        if ((long long)x > (long long)*d) *d = x;
-        break;
-      case AGG_BIT_AND:
-        *d &= x;
-        break;
-      case AGG_BIT_OR:
-        *d |= x;
-        break;
-      case AGG_BIT_XOR:
-        *d ^= x;
-        break;
+    const AggDesc& a = p.d[idx >> bits];
+    unsigned long long x = slo[idx];
+    long long h = 0;
+    if (a.op == AGG_SUM_INT && a.dst2) {
+      // total = shi * 2^32 + slo (slo < 2^63, |shi| < 2^62): exact in 128 bits
+      const __int128 t = ((__int128)shi[idx] << 32) + (__int128)x;
+      x = (unsigned long long)t;
+      h = (long long)(t >> 64);
     }
+    if (slices > 1) {
+      merge_global(a, g, x, h);   // (identity states are skipped)
+      continue;
+    }
+    unsigned long long lo = ((const unsigned long long*)a.dst)[g];
+    long long hi = a.op == AGG_SUM_INT && a.dst2 ? ((const long long*)a.dst2)[g] : 0;
+    combine(a.op, lo, hi, x, h);
+    store_exclusive(a, g, lo, hi);
   }
 }
 }  // namespace
@@ -1495,19 +1258,19 @@ void agg_partitioned(const int32_t* gid, int64_t n, int64_t ngroups, const AggDe
     p.vals[k] = vals ? vals[k] : nullptr;
   }
   const size_t lds = (size_t)nbk * sizeof(int32_t);
+  const char* what = "agg_partitioned";
   if (phase == 0) {
-    hipLaunchKernelGGL(aggp_count_kernel, dim3(kPartBlocks), dim3(kBlock), lds, stream, gid, n, ngroups, bits, nbk, cnt);
+    launch(what, aggp_count_kernel, dim3(kPartBlocks), dim3(kBlock), lds, stream, gid, n, ngroups, bits, nbk, cnt);
   } else if (phase == 1) {
-    hipLaunchKernelGGL(aggp_scatter_kernel, dim3(kPartBlocks), dim3(kBlock), lds, stream, gid, n, ngroups, bits, nbk,
-                       off, pg, p);
+    launch(what, aggp_scatter_kernel, dim3(kPartBlocks), dim3(kBlock), lds, stream, gid, n, ngroups, bits, nbk, off, pg,
+           p);
   } else {
     const size_t st = (size_t)nagg * ((size_t)1 << bits) * 16;
     // few buckets: enough workgroups to fill the chip (256 CUs), slices merged atomically
     const int slices = nbk >= 128 ? 1 : std::min(64, (256 + nbk - 1) / nbk);
-    hipLaunchKernelGGL(aggp_bucket_kernel, dim3(nbk * slices), dim3(kPartBlock2), st, stream, pg, off, total,
-                       kPartBlocks, ngroups, bits, slices, p);
+    launch(what, aggp_bucket_kernel, dim3(nbk * slices), dim3(kPartBlock2), st, stream, pg, off, total, kPartBlocks,
+           ngroups, bits, slices, p);
   }
-  check_launch("agg_partitioned", stream);
 }
 
 void key_histogram(const void* keys, bool key64, const uint8_t* valid, int64_t n, int64_t kmin, int64_t span,

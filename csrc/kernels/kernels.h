@@ -239,7 +239,8 @@ enum AggOp : int {
 
 struct AggDesc {
   int op;
-  int src64;             // integer sources: 1 = int64, 0 = int32
+  int src64;             // integer sources: 1 = int64, 0 = int32; 2 = int16, 3 = int8 for the
+                         // streaming HAVING kernel only (sorted_having rejects them elsewhere)
   const void* src;       // null for COUNT(*)
   const uint8_t* valid;  // null = all rows valid
   void* dst;             // [ngroups] 8-byte states

@@ -21,10 +21,16 @@ template <typename Tag> using type_of = typename Tag::type;
 struct wide { bool is64; };   // -> tag<int32_t> / tag<int64_t>
 struct uwide { bool is64; };  // -> tag<uint32_t> / tag<uint64_t>
                               // a plain bool -> std::false_type / std::true_type
+struct value_bytes { int n; };  // 0 (no values), 1, 2 or 4 -> std::integral_constant<int, n>
 
 template <typename F> void pick(wide w, F&& f) { w.is64 ? f(tag<int64_t>{}) : f(tag<int32_t>{}); }
 template <typename F> void pick(uwide w, F&& f) { w.is64 ? f(tag<uint64_t>{}) : f(tag<uint32_t>{}); }
 template <typename F> void pick(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F> void pick(value_bytes b, F&& f) {
+  using std::integral_constant;
+  b.n == 0 ? f(integral_constant<int, 0>{}) : b.n == 1 ? f(integral_constant<int, 1>{})
+  : b.n == 2 ? f(integral_constant<int, 2>{}) : f(integral_constant<int, 4>{});
+}
 
 // dispatch(flags..., f): call f with one tag per flag
 template <typename A, typename F> void dispatch(A a, F&& f) { pick(a, f); }

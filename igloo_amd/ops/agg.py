@@ -5,9 +5,8 @@ pass over the group ids. Integer SUMs are exact 128-bit; the result comes
 back as int64 when every group fits, else as an [g, 2] (lo, hi) tensor.
 
 Rows whose group id lies outside [0, ngroups) belong to no group, on every
-path. A group without a (non-NULL) row keeps the identity: 0 for SUM / COUNT,
-I64_MAX / I64_MIN for integer MIN / MAX, +inf / -inf for f64 MIN / MAX, -1 / 0
-/ 0 for AND / OR / XOR. f64 MIN / MAX order -inf < ... < +inf < NaN, a NaN of
+path. A group without a (non-NULL) row keeps the operator's identity
+(``IDENTITY`` below). f64 MIN / MAX order -inf < ... < +inf < NaN, a NaN of
 either sign being the one greatest value.
 """
 from __future__ import annotations
@@ -25,6 +24,15 @@ OPS = {"sum_int": 0, "sum_f64": 1, "count": 2, "min_int": 3, "max_int": 4, "min_
 _INT_OPS = ("sum_int", "min_int", "max_int", "and_int", "or_int", "xor_int")
 I64_MAX = 2**63 - 1
 I64_MIN = -(2**63)
+_INF = float("inf")
+#: op -> (identity of the 64-bit device state, what a group without a row
+#: reports): they differ for f64 MIN / MAX, whose states are ordered int64 images
+IDENTITY = {"sum_int": (0, 0), "sum_f64": (0, 0.0), "count": (0, 0), "min_int": (I64_MAX, I64_MAX),
+            "max_int": (I64_MIN, I64_MIN), "min_f64": (I64_MAX, _INF), "max_f64": (I64_MIN, -_INF),
+            "and_int": (-1, -1), "or_int": (0, 0), "xor_int": (0, 0)}
+#: AggDesc::src64 of an integer source; int16 / int8 only as a NULL-free SUM of
+#: sorted_having (its streaming kernel)
+_SRC_CODES = {torch.int64: 1, torch.int32: 0, torch.int16: 2, torch.int8: 3}
 
 Spec = Tuple[str, Optional[torch.Tensor], Optional[torch.Tensor]]  # (op, values, valid)
 
@@ -89,10 +97,50 @@ def _narrow_sums(specs, n) -> set:
             if op == "sum_int" and vals is not None and vals.dtype == torch.int32}
 
 
+def _descs(specs, posts, n, narrow_values=False) -> list:
+    """The (code, src64, src, valid, dst, dst2) descriptors of ``specs`` over
+    the states ``posts`` = [(op, dst, dst2)]."""
+    descs = []
+    for (op, vals, valid), (_op, dst, dst2) in zip(specs, posts):
+        src64 = 1
+        if vals is not None:
+            assert vals.numel() == n and vals.is_contiguous()
+            if op in _INT_OPS:
+                assert vals.dtype in _SRC_CODES, vals.dtype
+                src64 = _SRC_CODES[vals.dtype]
+                assert src64 < 2 or (narrow_values and op == "sum_int" and valid is None), \
+                    "int16 / int8 values: a NULL-free SUM of sorted_having only"
+            else:
+                assert vals.dtype == torch.float64 or op == "count"
+        descs.append((OPS[op], src64, ptr(vals), ptr(valid), ptr(dst), ptr(dst2)))
+    return descs
+
+
+def _results(posts, known=()) -> List[torch.Tensor]:
+    """Final states [(op, dst, dst2)] -> result tensors. One host sync for
+    every 128-bit integer SUM's "fits in int64" check (none for the specs in
+    ``known``, whose input has a readback-free bound proving it fits)."""
+    wide = [(dst, dst2) for si, (op, dst, dst2) in enumerate(posts)
+            if op == "sum_int" and dst2 is not None and si not in known]
+    fits = iter([1 - f for f in to_host_ints(_wide_flags(wide))] if wide and wide[0][0].numel() else [1] * len(wide))
+    outs = []
+    for si, (op, dst, dst2) in enumerate(posts):
+        if op == "sum_int":
+            ok = dst2 is None or si in known or next(fits)
+            outs.append(dst if ok else torch.stack([dst, dst2], dim=1))
+        elif op in ("min_f64", "max_f64"):
+            # empty groups keep the int64 sentinel: report +/-inf like the CPU path
+            sentinel, empty = IDENTITY[op]
+            outs.append(torch.where(dst == sentinel, torch.full_like(dst, 0).double() + empty, _ordered_to_f64(dst)))
+        else:
+            outs.append(dst)
+    return outs
+
+
 def _gpu(gid, ngroups, specs, n, device, sorted_gids=False) -> List[torch.Tensor]:
     N = native()
     g = max(ngroups, 1)
-    outs, descs, posts = [], [], []
+    posts = []
     narrow = _narrow_sums(specs, n)
     # every zero-initialised state of the call (sums, their carry words,
     # counts) in ONE zeroed buffer: one fill kernel instead of one per state
@@ -108,29 +156,16 @@ def _gpu(gid, ngroups, specs, n, device, sorted_gids=False) -> List[torch.Tensor
         z = zbuf[zi * slot: zi * slot + g]
         zi += 1
         return z.view(dt) if dt != torch.int64 else z
-    for si, (op, vals, valid) in enumerate(specs):
-        code = OPS[op]
+    for si, (op, _vals, _valid) in enumerate(specs):
         dst2 = None
         if op in ("sum_int", "sum_f64", "count"):
             dst = zeros(torch.float64 if op == "sum_f64" else torch.int64)
             if op == "sum_int" and si not in narrow:
                 dst2 = zeros()
-        elif op.startswith("min"):
-            dst = torch.full((g,), I64_MAX, dtype=torch.int64, device=device)
-        elif op in ("and_int", "or_int", "xor_int"):
-            dst = torch.full((g,), -1 if op == "and_int" else 0, dtype=torch.int64, device=device)
         else:
-            dst = torch.full((g,), I64_MIN, dtype=torch.int64, device=device)
-        src64 = 1
-        if vals is not None:
-            assert vals.numel() == n and vals.is_contiguous()
-            if op in _INT_OPS:
-                assert vals.dtype in (torch.int32, torch.int64), vals.dtype
-                src64 = 1 if vals.dtype == torch.int64 else 0
-            else:
-                assert vals.dtype == torch.float64 or op == "count"
-        descs.append((code, src64, ptr(vals), ptr(valid), ptr(dst), ptr(dst2)))
+            dst = torch.full((g,), IDENTITY[op][0], dtype=torch.int64, device=device)
         posts.append((op, dst, dst2))
+    descs = _descs(specs, posts, n)
     if n > 0:
         s = stream(gid if gid is not None else posts[0][1])
         for i in range(0, len(descs), 8):
@@ -140,26 +175,8 @@ def _gpu(gid, ngroups, specs, n, device, sorted_gids=False) -> List[torch.Tensor
                 continue
             launch("agg_update")
             N.agg_update(ptr(gid), n, ngroups if gid is not None else 1, chunk, s, bool(sorted_gids))
-    # one host sync for every 128-bit integer SUM's "fits in int64" check
-    # (none for a SUM whose input has a readback-free bound proving it fits)
-    known = {si for si, (op, vals, _v) in enumerate(specs) if op == "sum_int" and posts[si][2] is not None
-             and _sum_fits(vals, n)}
-    wide = [(dst, dst2) for si, (op, dst, dst2) in enumerate(posts)
-            if op == "sum_int" and dst2 is not None and si not in known]
-    fits = [1 - f for f in to_host_ints(_wide_flags(wide))] if wide else []
-    fit_iter = iter(fits)
-    for si, (op, dst, dst2) in enumerate(posts):
-        if op == "sum_int":
-            ok = dst2 is None or si in known or next(fit_iter)
-            outs.append(dst if ok else torch.stack([dst, dst2], dim=1))
-        elif op in ("min_f64", "max_f64"):
-            # empty groups keep the int64 sentinel: report +/-inf like the CPU path
-            sentinel = I64_MAX if op == "min_f64" else I64_MIN
-            inf = float("inf") if op == "min_f64" else float("-inf")
-            outs.append(torch.where(dst == sentinel, torch.full_like(dst, 0).double() + inf, _ordered_to_f64(dst)))
-        else:
-            outs.append(dst)
-    return outs
+    return _results(posts, {si for si, (op, vals, _v) in enumerate(specs)
+                            if op == "sum_int" and posts[si][2] is not None and _sum_fits(vals, n)})
 
 
 #: radix-partitioned aggregation (csrc/kernels/agg.hip agg_partitioned) for
@@ -238,19 +255,17 @@ def _cpu(gid, ngroups, specs, n) -> List[torch.Tensor]:
                 hi = torch.tensor([t >> 64 for t in tot], dtype=torch.int64)
                 outs.append(_wide_to_result(lo, hi))
         elif op in ("min_int", "max_int"):
-            init = I64_MAX if op == "min_int" else I64_MIN
-            base = torch.full((g,), init, dtype=torch.int64)
+            base = torch.full((g,), IDENTITY[op][1], dtype=torch.int64)
             outs.append(base.scatter_reduce(0, idx, v.to(torch.int64), reduce="amin" if op == "min_int" else "amax"))
         elif op in ("min_f64", "max_f64"):
             # the order is -inf < ... < +inf < NaN, every NaN one value (as the
             # GPU's ordered images, csrc/kernels/agg.hip f64_agg_key): MAX is
             # NaN once a group holds one, MIN only when it holds nothing else
             # (scatter_reduce alone would propagate NaN through both)
-            init = float("inf") if op == "min_f64" else float("-inf")
             v = v.to(torch.float64)
             nan = v != v
             num = ~nan
-            res = torch.full((g,), init, dtype=torch.float64).scatter_reduce(
+            res = torch.full((g,), IDENTITY[op][1], dtype=torch.float64).scatter_reduce(
                 0, idx[num], v[num], reduce="amin" if op == "min_f64" else "amax")
             to_nan = torch.zeros(g, dtype=torch.bool).index_fill_(0, idx[nan], True)
             if op == "min_f64":
@@ -259,7 +274,7 @@ def _cpu(gid, ngroups, specs, n) -> List[torch.Tensor]:
         elif op in ("and_int", "or_int", "xor_int"):
             import numpy as np
             ufn = {"and_int": np.bitwise_and, "or_int": np.bitwise_or, "xor_int": np.bitwise_xor}[op]
-            res = np.full(g, -1 if op == "and_int" else 0, dtype=np.int64)
+            res = np.full(g, IDENTITY[op][1], dtype=np.int64)
             if idx.numel():
                 order = torch.argsort(idx, stable=True)
                 gi_s = idx[order].numpy()
@@ -347,19 +362,10 @@ def sorted_having(keys: torch.Tensor, specs: Sequence[Spec], hidx: int, hop: str
     n = keys.numel()
     dev = keys.device
     cap = n // 64 + 4096
-    descs, posts = [], []
-    for op, vals, valid in specs:
-        dst = torch.empty(cap, dtype=torch.float64 if op == "sum_f64" else torch.int64, device=dev)
-        dst2 = torch.empty(cap, dtype=torch.int64, device=dev) if op == "sum_int" else None
-        src64 = 1
-        if vals is not None:
-            assert vals.numel() == n and vals.is_contiguous()
-            if op in _INT_OPS:
-                # int16 / int8 (codes 2 / 3): a NULL-free SUM for the streaming kernel only
-                src64 = {torch.int64: 1, torch.int32: 0, torch.int16: 2, torch.int8: 3}[vals.dtype]
-                assert src64 < 2 or (op == "sum_int" and valid is None), "narrow values: NULL-free SUM only"
-        descs.append((OPS[op], src64, ptr(vals), ptr(valid), ptr(dst), ptr(dst2)))
-        posts.append((op, dst, dst2))
+    # (a state per possible passing run; the kernel writes every one it reports)
+    posts = [(op, torch.empty(cap, dtype=torch.float64 if op == "sum_f64" else torch.int64, device=dev),
+              torch.empty(cap, dtype=torch.int64, device=dev) if op == "sum_int" else None) for op, _v, _m in specs]
+    descs = _descs(specs, posts, n, narrow_values=True)
     c = int(hconst) if not isinstance(hconst, float) else 0
     lo = ((c + 2**64) % 2**64) - (2**64 if ((c + 2**64) % 2**64) >= 2**63 else 0)
     hi = c >> 64
@@ -374,21 +380,8 @@ def sorted_having(keys: torch.Tensor, specs: Sequence[Spec], hidx: int, hop: str
     if overflow or m > cap:
         return None
     perm = argsort([(rep[:m], False, False, None)], m, dev) if m > 1 else torch.arange(m, device=dev)
-    rep = rep[:m].index_select(0, perm.long())
-    outs = []
-    wide = [(dst[:m].index_select(0, perm.long()), dst2[:m].index_select(0, perm.long()))
-            for op, dst, dst2 in posts if op == "sum_int"]
-    fits = iter([1 - f for f in to_host_ints(_wide_flags(wide))] if wide and m else [1] * len(wide))
-    witer = iter(wide)
-    for op, dst, dst2 in posts:
-        if op == "sum_int":
-            lo_, hi_ = next(witer)
-            outs.append(lo_ if next(fits) else torch.stack([lo_, hi_], dim=1))
-            continue
-        d = dst[:m].index_select(0, perm.long())
-        if op in ("min_f64", "max_f64"):
-            sentinel = I64_MAX if op == "min_f64" else I64_MIN
-            inf = float("inf") if op == "min_f64" else float("-inf")
-            d = torch.where(d == sentinel, torch.full_like(d, 0).double() + inf, _ordered_to_f64(d))
-        outs.append(d)
-    return rep, outs
+    perm = perm.long()
+
+    def take(t):
+        return None if t is None else t[:m].index_select(0, perm)
+    return take(rep), _results([(op, take(dst), take(dst2)) for op, dst, dst2 in posts])

@@ -1,7 +1,8 @@
 """Case generators and checkers shared by tests/test_groupby_ref.py (torch CPU
 paths) and tests/test_hash_tables_gpu.py / tests/test_agg_edges_gpu.py (gfx950
 kernels): every checker runs ``igloo_amd.ops.hashing`` / ``ops.agg`` on
-``device`` and compares with tests/groupby_ref.py. A plain helper module; the
+``device`` and compares with tests/groupby_ref.py (check_having_general: the
+run-folding HAVING kernel, GPU only). A plain helper module; the
 inputs are seeded, the references are cached per process so the files share
 them. The hash function of the tables is deliberately not reproduced here:
 the sentinel cases rely on numbers (twelve key sets) instead.
@@ -542,3 +543,55 @@ def check_agg(regime, nagg, masked, device, monkeypatch):
             op = AGG_SPECS[si][0]
             compare_agg(op, out, _agg_expect(regime, nagg, masked, si),
                         f"{regime} nagg={nagg} masked={masked} {op}({AGG_SPECS[si][1]})")
+
+
+# ------------------------------------------------- run-folding HAVING kernel
+HAVING_MAX_RUN = 256    # kHavingMaxRun of csrc/kernels/agg.hip: longer runs send the caller to the general path
+
+
+@functools.lru_cache(maxsize=None)
+def _having_runs(masked):
+    """(run start rows, run index per row) of the sorted regime's group ids
+    taken as keys: -1 and G+5 are ordinary keys here."""
+    k = agg_case("sorted", 8, masked).gid
+    first = np.r_[True, k[1:] != k[:-1]]
+    return np.flatnonzero(first), np.cumsum(first) - 1
+
+
+@functools.lru_cache(maxsize=None)
+def _having_expect(masked, si):
+    c = agg_case("sorted", 8, masked)
+    starts, run = _having_runs(masked)
+    op, col = AGG_SPECS[si]
+    return R.agg_ref(run.tolist(), len(starts), op, None if col is None else c.cols[col].tolist(),
+                     None if c.valid is None else c.valid.tolist(), n=c.n)
+
+
+def check_having_general(masked, device, monkeypatch):
+    """Every operator through the run-folding sorted_having_kernel
+    (IGLOO_DEBUG=having_general), three aggregates plus the COUNT(*) that
+    HAVING compares (>= 1: every run passes) per launch, against agg_ref over
+    the run index as group id."""
+    monkeypatch.setenv("IGLOO_DEBUG", "having_general")     # (C++ reads it per call)
+    c = agg_case("sorted", 8, masked)
+    assert c.n == AGG_ROWS and (np.diff(c.gid) >= 0).all()
+    starts, _run = _having_runs(masked)
+    lens = np.diff(np.r_[starts, c.n])
+    # the kernel's limits, from the data: else it reports overflow and returns None
+    assert lens.max() < HAVING_MAX_RUN and len(starts) <= c.n // 64 + 4096
+    keys = dev_t(c.gid, device)
+    valid = dev_t(c.valid, device)
+    cols = {k: dev_t(v, device) for k, v in c.cols.items()}
+    for i in range(0, len(AGG_SPECS), 3):
+        chunk = list(range(i, min(i + 3, len(AGG_SPECS))))
+        specs = [(AGG_SPECS[si][0], None if AGG_SPECS[si][1] is None else cols[AGG_SPECS[si][1]], valid) for si in chunk]
+        specs.append(("count", None, None))
+        before = KERNEL_CALLS["sorted_having"]
+        got = A.sorted_having(keys, specs, len(specs) - 1, ">=", 1)
+        assert got is not None, "a run past the kernel's limits"
+        assert KERNEL_CALLS["sorted_having"] > before
+        rep, outs = got
+        assert np.array_equal(rep.cpu().numpy(), starts) and np.array_equal(outs[-1].cpu().numpy(), lens)
+        for si, out in zip(chunk, outs):
+            op = AGG_SPECS[si][0]
+            compare_agg(op, out, _having_expect(masked, si), f"having_general masked={masked} {op}({AGG_SPECS[si][1]})")

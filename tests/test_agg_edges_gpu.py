@@ -22,3 +22,10 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("regime", C.REGIMES)
 def test_grouped_aggregate_edges(gpu_device, regime, nagg, masked, monkeypatch):
     C.check_agg(regime, nagg, masked, gpu_device, monkeypatch)
+
+
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "mask"])
+def test_having_general_kernel_edges(gpu_device, masked, monkeypatch):
+    """The run-folding sorted_having_kernel has a fold path of its own: the
+    sorted regime's rows, their group ids as keys, every operator."""
+    C.check_having_general(masked, gpu_device, monkeypatch)
