@@ -35,9 +35,16 @@ constexpr int kRsTile = kBlock * kRsItems;  // 4096 rows per workgroup
 constexpr int kRadix = 256;
 static_assert(kBlock == kRadix, "one lane per digit in the per-tile scans");
 
+// dmask: the digit's bits that lie below end_bit (digit_mask), so that the
+// last pass of a range whose width is no multiple of 8 ignores the key bits at
+// and above end_bit
 template <typename K>
-__device__ inline uint32_t digit_of(K k, int shift) {
-  return (uint32_t)(k >> shift) & (kRadix - 1);
+__device__ inline uint32_t digit_of(K k, int shift, uint32_t dmask) {
+  return (uint32_t)(k >> shift) & dmask;
+}
+
+__host__ __device__ inline uint32_t digit_mask(int shift, int end_bit) {
+  return end_bit - shift >= 8 ? (uint32_t)(kRadix - 1) : ((1u << (end_bit - shift)) - 1u);
 }
 
 // mask of active lanes whose digit equals this lane's
@@ -56,13 +63,13 @@ __device__ inline uint64_t match_digit(uint32_t d, bool valid) {
 // r[j] = number of earlier items of the wave with the same digit.
 // wcnt: this wave's 256 running counters in LDS (zeroed by the caller).
 template <typename K>
-__device__ inline void rank_wave(const K (&k)[kRsItems], const bool (&ok)[kRsItems], int shift, int32_t* wcnt,
-                                 int32_t (&r)[kRsItems]) {
+__device__ inline void rank_wave(const K (&k)[kRsItems], const bool (&ok)[kRsItems], int shift, uint32_t dmask,
+                                 int32_t* wcnt, int32_t (&r)[kRsItems]) {
   const int lane = lane_id();
   const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
   for (int j = 0; j < kRsItems; ++j) {
-    const uint32_t d = digit_of(k[j], shift);
+    const uint32_t d = digit_of(k[j], shift, dmask);
     const uint64_t m = match_digit(d, ok[j]);
     const int pre = __popcll(m & below);
     int32_t base = 0;
@@ -91,7 +98,8 @@ __device__ inline void tile_digit_scan(int32_t (*wcnt)[kRadix], int32_t* dstart,
 
 template <typename K>
 __global__ __launch_bounds__(kBlock) void rs_hist_kernel(const K* __restrict__ keys, int64_t n, int shift,
-                                                         int32_t* __restrict__ counts, int64_t tiles) {
+                                                         uint32_t dmask, int32_t* __restrict__ counts,
+                                                         int64_t tiles) {
   __shared__ int32_t wh[kWavesPerBlock][kRadix];
   const int w = threadIdx.x / kWave, lane = lane_id();
   for (int i = threadIdx.x; i < kWavesPerBlock * kRadix; i += kBlock) (&wh[0][0])[i] = 0;
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void rs_hist_kernel(const K* __restrict__ k
   const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll
   for (int j = 0; j < kRsItems; ++j) {
-    const uint32_t d = digit_of(k[j], shift);
+    const uint32_t d = digit_of(k[j], shift, dmask);
     const uint64_t m = match_digit(d, ok[j]);
     if (ok[j] && __popcll(m & below) == 0) wh[w][d] += __popcll(m);
   }
@@ -123,8 +131,8 @@ __global__ __launch_bounds__(kBlock) void rs_hist_kernel(const K* __restrict__ k
 template <typename K, typename V>
 __global__ __launch_bounds__(kBlock) void rs_scatter_kernel(const K* __restrict__ kin, const V* __restrict__ vin,
                                                             K* __restrict__ kout, V* __restrict__ vout, int64_t n,
-                                                            int shift, const int64_t* __restrict__ offsets,
-                                                            int64_t tiles) {
+                                                            int shift, uint32_t dmask,
+                                                            const int64_t* __restrict__ offsets, int64_t tiles) {
   __shared__ int32_t wcnt[kWavesPerBlock][kRadix];
   __shared__ int32_t dstart[kRadix];
   __shared__ int64_t gofs[kRadix];
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void rs_scatter_kernel(const K* __restrict_
     v[j] = ok[j] ? vin[i] : V(0);
   }
   int32_t r[kRsItems];
-  rank_wave(k, ok, shift, wcnt[w], r);
+  rank_wave(k, ok, shift, dmask, wcnt[w], r);
   __syncthreads();
   tile_digit_scan(wcnt, dstart, scratch);
   {
@@ -158,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void rs_scatter_kernel(const K* __restrict_
 #pragma unroll
   for (int j = 0; j < kRsItems; ++j) {
     if (!ok[j]) continue;
-    const uint32_t d = digit_of(k[j], shift);
+    const uint32_t d = digit_of(k[j], shift, dmask);
     const int pos = dstart[d] + wcnt[w][d] + r[j];
     sk[pos] = k[j];
     sv[pos] = v[j];
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void rs_scatter_kernel(const K* __restrict_
   const int cnt = (int)((n - tile0) < kRsTile ? (n - tile0) : kRsTile);
   for (int i = threadIdx.x; i < cnt; i += kBlock) {
     const K key = sk[i];
-    const int64_t g = gofs[digit_of(key, shift)] + i;
+    const int64_t g = gofs[digit_of(key, shift, dmask)] + i;
     kout[g] = key;
     vout[g] = sv[i];
   }
@@ -286,17 +294,18 @@ __global__ __launch_bounds__(kBlock) void rs_small_kernel(K* __restrict__ keys, 
   }
   for (int shift = begin_bit; shift < end_bit; shift += 8) {
     if (((diff >> shift) & K(kRadix - 1)) == K(0)) continue;  // every key has the same digit here
+    const uint32_t dmask = digit_mask(shift, end_bit);
     for (int i = threadIdx.x; i < kWavesPerBlock * kRadix; i += kBlock) (&wcnt[0][0])[i] = 0;
     __syncthreads();
     int32_t r[kRsItems];
-    rank_wave(k, ok, shift, wcnt[w], r);
+    rank_wave(k, ok, shift, dmask, wcnt[w], r);
     __syncthreads();
     tile_digit_scan(wcnt, dstart, scratch);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < kRsItems; ++j) {
       if (!ok[j]) continue;
-      const uint32_t d = digit_of(k[j], shift);
+      const uint32_t d = digit_of(k[j], shift, dmask);
       const int pos = dstart[d] + wcnt[w][d] + r[j];
       sk[pos] = k[j];
       sv[pos] = v[j];
@@ -341,12 +350,13 @@ int radix_sort_impl(K* k0, K* k1, V* v0, V* v1, int64_t n, int begin_bit, int en
   K* kb[2] = {k0, k1};
   V* vb[2] = {v0, v1};
   for (int shift = begin_bit; shift < end_bit; shift += 8) {
-    hipLaunchKernelGGL((rs_hist_kernel<K>), dim3((unsigned)tiles), dim3(kBlock), 0, stream, kb[cur], n, shift,
+    const uint32_t dmask = digit_mask(shift, end_bit);
+    hipLaunchKernelGGL((rs_hist_kernel<K>), dim3((unsigned)tiles), dim3(kBlock), 0, stream, kb[cur], n, shift, dmask,
                        counts, tiles);
     check_launch("sort.hist", stream);
     exclusive_scan(counts, false, m, offsets, scan_ws, scan_ws + scan_tiles, stream);
     hipLaunchKernelGGL((rs_scatter_kernel<K, V>), dim3((unsigned)tiles), dim3(kBlock), 0, stream, kb[cur], vb[cur],
-                       kb[cur ^ 1], vb[cur ^ 1], n, shift, offsets, tiles);
+                       kb[cur ^ 1], vb[cur ^ 1], n, shift, dmask, offsets, tiles);
     check_launch("sort.scatter", stream);
     cur ^= 1;
   }
@@ -354,6 +364,10 @@ int radix_sort_impl(K* k0, K* k1, V* v0, V* v1, int64_t n, int begin_bit, int en
 }
 
 // ---------------------------------------------------------------- key packing
+// The ordered code of the quiet NaN 0x7ff8... / 0x7fc0...: a NaN of either sign
+// and any payload sorts as this one value (ops/sort.py _ordered_f64 / _ordered_f32).
+constexpr uint64_t kNanCode64 = 0xfff8000000000000ull;
+constexpr uint64_t kNanCode32 = 0xffc00000ull;
 __device__ inline uint64_t ordered_bits(const SortKeyCol& c, int64_t row) {
   switch (c.kind) {
     case 0: {  // signed integer of c.width bytes
@@ -364,11 +378,12 @@ __device__ inline uint64_t ordered_bits(const SortKeyCol& c, int64_t row) {
       else v = reinterpret_cast<const int8_t*>(c.ptr)[row];
       return (uint64_t)v ^ 0x8000000000000000ull;
     }
-    case 1: {  // float64: total order (-0.0 folded onto +0.0 by the host bounds)
+    case 1: {  // float64: total order, -0.0 folded onto +0.0, every NaN onto one code above +inf's
       double d = reinterpret_cast<const double*>(c.ptr)[row];
       if (d == 0.0) d = 0.0;
       uint64_t b;
       __builtin_memcpy(&b, &d, 8);
+      if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return kNanCode64;
       return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
     }
     case 2:  // unsigned byte / bool
@@ -378,6 +393,7 @@ __device__ inline uint64_t ordered_bits(const SortKeyCol& c, int64_t row) {
       if (f == 0.0f) f = 0.0f;
       uint32_t b;
       __builtin_memcpy(&b, &f, 4);
+      if ((b & 0x7fffffffu) > 0x7f800000u) return kNanCode32;
       return (b >> 31) ? (uint64_t)(~b) : (uint64_t)(b | 0x80000000u);
     }
   }

@@ -5,9 +5,17 @@ ORDER BY keys are packed on the device into ONE order-preserving unsigned key
 per row (``sort_key_pack``): each column contributes a field of
 ``bitlen(max - min)`` bits (DESC flips it inside its span, a nullable column
 adds a NULL-order bit above it), so e.g. (l_returnflag, l_linestatus) packs
-into 3 bits and sorts in one 8-bit pass. Column sets wider than 64 bits are
-split into groups sorted least-significant group first (stable LSD). The
+into 3 bits and sorts in one 8-bit pass. Column sets wider than 64 bits (or
+of more columns than one pack launch takes) are split into groups sorted
+least-significant group first (stable LSD); a nullable column whose values
+need all 64 bits gives its NULL flag a more significant field of its own. The
 sort carries the row id as its value, so the result is a permutation.
+
+The order: columns most significant first, remaining ties by row id; NULLs
+tie with each other and go where ``nulls_first`` says, whatever ``desc`` says,
+and the value under a NULL slot never matters; floats order as -inf < ... <
+-0.0 = +0.0 < ... < +inf < NaN, a NaN of either sign and any payload being one
+value; ``desc`` reverses the values, not the tied rows.
 
 ``topk`` (ORDER BY ... LIMIT k) radix-selects first: histograms of the top
 key digits (refined within the boundary bucket while it is large) find a
@@ -40,7 +48,15 @@ _FULL = {torch.int8: (-(1 << 7), (1 << 7) - 1), torch.int16: (-(1 << 15), (1 << 
 SMALL_SORT = 4096
 
 
+#: sort.hip kMaxSortCols: columns one ``sort_key_pack`` launch takes
+MAX_PACK_COLS = 8
+
+
 def _ordered_f64(x: float) -> int:
+    """Order-preserving unsigned code of a float64 (sort.hip ordered_bits):
+    -inf < ... < -0.0 = +0.0 < ... < +inf < NaN, every NaN one code."""
+    if x != x:
+        return 0xFFF8000000000000
     if x == 0.0:
         x = 0.0
     b = struct.unpack("<Q", struct.pack("<d", x))[0]
@@ -48,14 +64,28 @@ def _ordered_f64(x: float) -> int:
 
 
 def _ordered_f32(x: float) -> int:
+    if x != x:
+        return 0xFFC00000
     if x == 0.0:
         x = 0.0
     b = struct.unpack("<I", struct.pack("<f", x))[0]
     return (~b & 0xFFFFFFFF) if b >> 31 else (b | (1 << 31))
 
 
+def _float_codes(x: torch.Tensor) -> torch.Tensor:
+    """Signed image of the ordered code of every float (code - 2^63 as int64,
+    code - 2^31 as int32), except that a NaN keeps its magnitude bits: some
+    code above +inf's, folded onto the canonical one by ``_fields_from``.
+    Integer tensors, so the bounds come from ``_int_bounds`` and no NaN can
+    poison them (``aminmax`` answers NaN for both once one is present)."""
+    it, top = (torch.int64, (1 << 63) - 1) if x.dtype == torch.float64 else (torch.int32, (1 << 31) - 1)
+    m = x.contiguous().view(it) & top
+    return torch.where(x < 0, ~m, m)     # -0.0 and -NaN are not < 0: they take +0.0's and +NaN's side
+
+
 def _fields(keys: Sequence[SortKey]) -> List[tuple]:
-    """Per column: (tensor, valid, lo, span, kind, width, bits, desc, nulls_first). One host sync for all bounds."""
+    """Per key field (one per column, two for a 64-bit nullable one: see _fields_from):
+    (tensor, valid, lo, span, kind, width, bits, desc, nulls_first). One host sync for all bounds."""
     from .hashing import key_bound
     known = []
     for v, _desc, _nf, valid in keys:
@@ -80,6 +110,8 @@ def _fields(keys: Sequence[SortKey]) -> List[tuple]:
             stats.append(torch.zeros(2, dtype=torch.int64, device=v.device))
             continue
         x = v.to(torch.uint8) if v.dtype == torch.bool else v
+        if x.dtype in (torch.float64, torch.float32):
+            x = _float_codes(x)
         if is_gpu(x) and x.dtype in (torch.int32, torch.int64):
             # bounds from the hand-written two-stage reduction (util.hip): the
             # ATen aminmax zeroes its multi-block semaphores with a memset that
@@ -87,15 +119,17 @@ def _fields(keys: Sequence[SortKey]) -> List[tuple]:
             stats.append(_int_bounds(x))
             continue
         mn, mx = torch.aminmax(x)
-        if x.dtype in (torch.float64, torch.float32):
-            stats.append(torch.stack([mn.to(torch.float64), mx.to(torch.float64)]).view(torch.int64))
-        else:
-            stats.append(torch.stack([mn.to(torch.int64), mx.to(torch.int64)]))
+        stats.append(torch.stack([mn.to(torch.int64), mx.to(torch.int64)]))
     vals = to_host_ints(torch.cat(stats)) if stats else []
     return _fields_from(keys, vals)
 
 
 def _fields_from(keys: Sequence[SortKey], vals: Sequence[int]) -> List[tuple]:
+    """``vals``: per column the least and greatest value, floats as the signed
+    images of their ordered codes (``_float_codes``). A nullable column whose
+    value field takes all 64 bits has no room for its NULL flag: it yields two
+    fields, the flag (the validity bytes as a 1-bit column of its own) and,
+    less significant, the values with every NULL slot zeroed."""
     out = []
     for i, (v, desc, nf, valid) in enumerate(keys):
         if v.dtype not in _KIND:
@@ -107,14 +141,17 @@ def _fields_from(keys: Sequence[SortKey], vals: Sequence[int]) -> List[tuple]:
         elif kind == 2:
             lo, hi = a, b
         else:
-            fa, fb = struct.unpack("<2d", struct.pack("<2q", a, b))
-            enc = _ordered_f64 if kind == 1 else _ordered_f32
-            lo, hi = enc(fa), enc(fb)
+            enc, top = (_ordered_f64, 1 << 63) if kind == 1 else (_ordered_f32, 1 << 31)
+            inf, nan = enc(float("inf")), enc(float("nan"))
+            lo, hi = (nan if c > inf else c for c in (a + top, b + top))
         if v.numel() == 0:
             lo = hi = 0
         span = max(hi - lo, 0)
         bits = span.bit_length()
         t = v if v.dtype != torch.bool else v.view(torch.uint8)
+        if valid is not None and bits == 64:
+            out.append((valid.contiguous().view(torch.uint8), None, 0, 1, 2, 1, 1, int(not nf), 0))
+            t, valid = torch.where(valid, t, torch.zeros_like(t)), None
         out.append((t.contiguous(), None if valid is None else valid.contiguous(), lo & U64, span, kind, width,
                     bits, int(desc), int(nf)))
     return out
@@ -130,11 +167,12 @@ def _int_bounds(x: torch.Tensor) -> torch.Tensor:
 
 
 def _groups(fields: List[tuple]) -> List[List[tuple]]:
-    """Split columns (most significant first) into runs of <= 64 key bits."""
+    """Split columns (most significant first) into runs of <= 64 key bits and
+    <= MAX_PACK_COLS columns."""
     groups, cur, used = [], [], 0
     for f in fields:
         w = f[6] + (1 if f[1] is not None else 0)
-        if cur and used + w > 64:
+        if cur and (used + w > 64 or len(cur) == MAX_PACK_COLS):
             groups.append(cur)
             cur, used = [], 0
         cur.append(f)
@@ -164,9 +202,15 @@ def sort_pairs(keys: torch.Tensor, vals: torch.Tensor, end_bit: int, begin_bit: 
     being copied)."""
     n = keys.numel()
     if not is_gpu(keys):
+        if n <= 1 or end_bit <= begin_bit:
+            return keys.clone(), vals.clone()
         k = keys.to(torch.int64)
         if keys.dtype == torch.int32:
             k = k & 0xFFFFFFFF
+        if begin_bit > 0:   # logical shift of the unsigned key
+            k = (k >> begin_bit) & ((1 << (64 - begin_bit)) - 1)
+        if end_bit - begin_bit < 64:
+            k = k & ((1 << (end_bit - begin_bit)) - 1)
         else:  # unsigned 64-bit order on a signed tensor: flip the sign bit
             k = k ^ torch.tensor(-(1 << 63), dtype=torch.int64)
         o = torch.sort(k, stable=True).indices
