@@ -30,7 +30,8 @@ T* P(uintptr_t p) {
 }
 hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-// raw<&f>: f with each pointer parameter taken as uintptr_t; all else unchanged
+// raw<&f>: f with each pointer parameter taken as uintptr_t; all else unchanged (a bound struct such
+// as kern::JoinTableRef, taken by const reference, passes through as that reference)
 template <typename T>
 struct py_arg {
   using type = T;
@@ -310,48 +311,30 @@ PYBIND11_MODULE(_native, m) {
   m.def("radix_le_mask", raw<&kern::radix_le_mask>);
 
   // ------------------------------------------------------------ hash tables
-  m.def("join_build", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t tkeys, uintptr_t thead,
-                         bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t dups, uintptr_t bits,
-                         uint64_t bmask, uintptr_t s) {
-    if (n > 0 && (!keys || !thead || !dups || (!direct && !tkeys))) throw std::runtime_error("join_build: null buffer");
-    kern::join_build(P<const void>(keys), key64, P<const uint8_t>(valid), n, P<int64_t>(tkeys), P<void>(thead), rid64,
-                     cap, kmin, direct, P<unsigned long long>(dups), P<uint32_t>(bits), bmask, S(s));
-  });
-  m.def("join_csr_count", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t tkeys, uintptr_t cnt,
-                             bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t s) {
-    if (n > 0 && (!keys || !cnt || (!direct && !tkeys))) throw std::runtime_error("join_csr_count: null buffer");
-    kern::join_csr_count(P<const void>(keys), key64, P<const uint8_t>(valid), n, P<const int64_t>(tkeys),
-                         P<void>(cnt), rid64, cap, kmin, direct, S(s));
-  });
-  m.def("join_csr_scatter", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t n, uintptr_t tkeys, uintptr_t cnt,
-                               uintptr_t cstart, uintptr_t crows, bool rid64, int64_t cap, int64_t kmin, bool direct,
-                               uintptr_t s) {
-    if (n > 0 && (!keys || !cnt || !cstart || !crows || (!direct && !tkeys)))
-      throw std::runtime_error("join_csr_scatter: null buffer");
-    kern::join_csr_scatter(P<const void>(keys), key64, P<const uint8_t>(valid), n, P<const int64_t>(tkeys),
-                           P<void>(cnt), P<const void>(cstart), P<void>(crows), rid64, cap, kmin, direct, S(s));
-  });
-  m.def("join_probe", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
-                         uintptr_t cstart, uintptr_t crows, bool rid64, int64_t cap, int64_t kmin, bool direct,
-                         uintptr_t counts, uintptr_t first, uintptr_t matched, uintptr_t bits, uint64_t bmask,
-                         uintptr_t s) {
-    if (m_ > 0 && (!keys || !thead || (!direct && !tkeys) || (!cstart != !crows)))
-      throw std::runtime_error("join_probe: null buffer");
-    kern::join_probe(P<const void>(keys), key64, P<const uint8_t>(valid), m_, P<const int64_t>(tkeys),
-                     P<const void>(thead), P<const void>(cstart), P<const void>(crows), rid64, cap, kmin, direct,
-                     P<int32_t>(counts), P<void>(first), P<uint8_t>(matched), P<const uint32_t>(bits), bmask, S(s));
-  });
+  // A join table and a key column, described once (kernels.h): value classes built from pointers as
+  // unsigned integers, like every py_arg<T*>, and handed to the entry points by reference. The
+  // table's fields go by name only: positions of the same type cannot be swapped.
+  py::class_<kern::JoinTableRef>(m, "JoinTableRef")
+      .def(py::init([](uintptr_t tkeys, uintptr_t thead, uintptr_t cstart, uintptr_t crows, bool rid64, int64_t cap,
+                       int64_t kmin, bool direct, uintptr_t bits, uint64_t bmask, uintptr_t fold, int64_t n_build) {
+             return kern::JoinTableRef{P<int64_t>(tkeys), P<void>(thead), P<void>(cstart), P<void>(crows),
+                                       rid64,             cap,            kmin,            direct,
+                                       P<uint32_t>(bits), bmask,          P<uint32_t>(fold), n_build};
+           }),
+           py::kw_only(), py::arg("tkeys"), py::arg("thead"), py::arg("cstart") = 0, py::arg("crows") = 0,
+           py::arg("rid64"), py::arg("cap"), py::arg("kmin"), py::arg("direct"), py::arg("bits") = 0,
+           py::arg("bmask") = 0, py::arg("fold") = 0, py::arg("n_build"));
+  py::class_<kern::KeyColumn>(m, "KeyColumn")
+      .def(py::init([](uintptr_t keys, bool key64, uintptr_t valid, int64_t n) {
+             return kern::KeyColumn{P<const void>(keys), key64, P<const uint8_t>(valid), n};
+           }),
+           py::arg("keys"), py::arg("key64"), py::arg("valid"), py::arg("n"));
+  m.def("join_build", raw<&kern::join_build>);
+  m.def("join_csr_count", raw<&kern::join_csr_count>);
+  m.def("join_csr_scatter", raw<&kern::join_csr_scatter>);
+  m.def("join_probe", raw<&kern::join_probe>);
   m.def("probe_hit_tiles", &kern::probe_hit_tiles);
-  m.def("probe_hits", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
-                         bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t bits, uint64_t bmask,
-                         bool negate, int64_t n_build, uintptr_t fold, uintptr_t words, uintptr_t tile_counts,
-                         uintptr_t s) {
-    if (m_ > 0 && (!keys || !thead || !words || !tile_counts || (!direct && !tkeys)))
-      throw std::runtime_error("probe_hits: null buffer");
-    kern::probe_hits(P<const void>(keys), key64, P<const uint8_t>(valid), m_, P<const int64_t>(tkeys),
-                     P<const void>(thead), rid64, cap, kmin, direct, P<const uint32_t>(bits), bmask, negate, n_build,
-                     P<const uint32_t>(fold), P<unsigned long long>(words), P<int64_t>(tile_counts), S(s));
-  });
+  m.def("probe_hits", raw<&kern::probe_hits>);
   m.def("set_probe_grid_cap", &kern::set_probe_grid_cap);
   m.def("set_probe_bits", &kern::set_probe_bits);
   m.def("set_probe_stream_min_rows", &kern::set_probe_stream_min_rows);
@@ -370,26 +353,8 @@ PYBIND11_MODULE(_native, m) {
     kern::join_table_init(P<void>(thead), rid64, cap, P<int64_t>(tkeys), P<uint32_t>(bits), nbw,
                           P<unsigned long long>(dups), S(s));
   });
-  m.def("probe_write", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
-                          bool rid64, int64_t cap, int64_t kmin, bool direct, uintptr_t words, uintptr_t tile_off,
-                          uintptr_t out_probe, bool out64, uintptr_t out_build, int64_t out_cap, uintptr_t s) {
-    if (m_ > 0 && (!keys || !thead || !words || !tile_off || !out_probe || (!direct && !tkeys)))
-      throw std::runtime_error("probe_write: null buffer");
-    kern::probe_write(P<const void>(keys), key64, P<const uint8_t>(valid), m_, P<const int64_t>(tkeys),
-                      P<const void>(thead), rid64, cap, kmin, direct, P<const unsigned long long>(words),
-                      P<const int64_t>(tile_off), P<void>(out_probe), out64, P<void>(out_build), out_cap, S(s));
-  });
-  m.def("join_expand", [](uintptr_t keys, bool key64, uintptr_t valid, int64_t m_, uintptr_t tkeys, uintptr_t thead,
-                          uintptr_t cstart, uintptr_t crows, bool rid64, int64_t cap, int64_t kmin, bool direct,
-                          uintptr_t offsets, uintptr_t out_probe, uintptr_t out_build, uintptr_t bits, uint64_t bmask,
-                          int64_t out_cap, uintptr_t s) {
-    if (m_ > 0 && (!keys || !thead || !offsets || !out_probe || !out_build || (!direct && !tkeys)))
-      throw std::runtime_error("join_expand: null buffer");
-    kern::join_expand(P<const void>(keys), key64, P<const uint8_t>(valid), m_, P<const int64_t>(tkeys),
-                      P<const void>(thead), P<const void>(cstart), P<const void>(crows), rid64, cap, kmin, direct,
-                      P<const int64_t>(offsets), P<int32_t>(out_probe), P<void>(out_build), P<const uint32_t>(bits),
-                      bmask, out_cap, S(s));
-  });
+  m.def("probe_write", raw<&kern::probe_write>);
+  m.def("join_expand", raw<&kern::join_expand>);
   // fused scan kernels. cols: [(ptr, width)], terms: [(col, kind, lo, hi, set)],
   // keys: [(col, lo, mul)], aggs: [(op, checked, [(col, a, b)], dst, dst2, shared)]
   using FfCols = std::vector<std::pair<uintptr_t, int64_t>>;

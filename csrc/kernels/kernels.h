@@ -161,26 +161,42 @@ void hll_sketch(const void* keys, bool key64, const uint8_t* valid, int64_t n, u
                 hipStream_t stream);
 
 // ---- hashtable.hip -----------------------------------------------------------
-// bits/bmask: optional Bloom filter (bits: (bmask+1)/32 words, zeroed before
-// join_build; nullptr disables it on build or probe)
-// Row ids (thead, CSR cstart/crows, first / build-row outputs) are int32 when
-// rid64 is false (build side < 2^31 rows) and int64 otherwise.
-void join_build(const void* keys, bool key64, const uint8_t* valid, int64_t n, int64_t* tkeys, void* thead, bool rid64,
-                int64_t cap, int64_t kmin, bool direct, unsigned long long* dups, uint32_t* bits, uint64_t bmask,
-                hipStream_t stream);
+// A join table, described once for every entry point below. Row ids (thead,
+// the CSR cstart / crows, first / build-row outputs) are int32 when rid64 is
+// false (build side < 2^31 rows) and int64 otherwise.
+struct JoinTableRef {
+  int64_t* tkeys;   // hashed: cap + 1 keys; unused by a direct table
+  void* thead;      // head row per slot
+  void* cstart;     // CSR runs of a duplicate-key build: cap + 1 run starts and the
+  void* crows;      // build rows in run order; both null for a unique build
+  bool rid64;
+  int64_t cap, kmin;
+  bool direct;
+  uint32_t* bits;   // optional Bloom filter / exact bitmap ((bmask + 1) / 32 or (cap + 31) / 32 words,
+  uint64_t bmask;   // zeroed before join_build): null when the table has none
+  uint32_t* fold;   // probe_fold_build's scratch (null: not built)
+  int64_t n_build;  // build rows
+};
+// A key column of n rows (build or probe side); valid null: no NULL keys
+struct KeyColumn {
+  const void* keys;
+  bool key64;
+  const uint8_t* valid;
+  int64_t n;
+};
+// throws "<what>: null buffer" unless thead is set, tkeys is set or the table direct, and cstart / crows
+// are both set or both null
+void check(const JoinTableRef& t, const char* what);
+// The entry points check() their table first. use_filter (per probe call): consult the table's bits;
+// the build always sets them.
+void join_build(const JoinTableRef& t, const KeyColumn& build, unsigned long long* dups, hipStream_t stream);
 // CSR runs of a duplicate-key build: cnt[cap+1] zeroed -> per-slot counts;
 // cstart = exclusive scan of cnt (cap+1 entries); scatter fills crows[n] and
 // consumes cnt
-void join_csr_count(const void* keys, bool key64, const uint8_t* valid, int64_t n, const int64_t* tkeys, void* cnt,
-                    bool rid64, int64_t cap, int64_t kmin, bool direct, hipStream_t stream);
-void join_csr_scatter(const void* keys, bool key64, const uint8_t* valid, int64_t n, const int64_t* tkeys, void* cnt,
-                      const void* cstart, void* crows, bool rid64, int64_t cap, int64_t kmin, bool direct,
-                      hipStream_t stream);
-// cstart/crows null: unique build (thead only)
-void join_probe(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                const void* thead, const void* cstart, const void* crows, bool rid64, int64_t cap, int64_t kmin,
-                bool direct, int32_t* counts, void* first, uint8_t* build_matched, const uint32_t* bits,
-                uint64_t bmask, hipStream_t stream);
+void join_csr_count(const JoinTableRef& t, const KeyColumn& build, void* cnt, hipStream_t stream);
+void join_csr_scatter(const JoinTableRef& t, const KeyColumn& build, void* cnt, hipStream_t stream);
+void join_probe(const JoinTableRef& t, const KeyColumn& probe, bool use_filter, int32_t* counts, void* first,
+                uint8_t* build_matched, hipStream_t stream);
 // first-match probe as a row selection: pass 1 hit bits (words[tiles*128]) + per-tile counts, pass 2
 // (tile_off = exclusive scan of the counts) writes hit rows (+ their build rows) in row order
 int64_t probe_hit_tiles(int64_t m);
@@ -197,22 +213,17 @@ const char* last_probe_kernel();
 // is wider than the fold: probe_hits then needs probe_fold_build's probe_fold_words() words
 bool probe_fold_needed(int64_t m, int64_t cap);
 void probe_fold_build(const uint32_t* bits, int64_t cap, uint32_t* fold, hipStream_t stream);
-void probe_hits(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const uint32_t* bits,
-                uint64_t bmask, bool negate, int64_t n_build, const uint32_t* fold, unsigned long long* words,
-                int64_t* tile_counts, hipStream_t stream);
+void probe_hits(const JoinTableRef& t, const KeyColumn& probe, bool use_filter, bool negate,
+                unsigned long long* words, int64_t* tile_counts, hipStream_t stream);
 // thead[cap] = -1, tkeys[cap] = the empty key (null: a direct table), bits[nbw] = 0 (null: none), dups = 0
 // in one launch; the buffers are 16-byte aligned
 void join_table_init(void* thead, bool rid64, int64_t cap, int64_t* tkeys, uint32_t* bits, int64_t nbw,
                      unsigned long long* dups, hipStream_t stream);
-void probe_write(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                 const void* thead, bool rid64, int64_t cap, int64_t kmin, bool direct, const unsigned long long* words,
+void probe_write(const JoinTableRef& t, const KeyColumn& probe, const unsigned long long* words,
                  const int64_t* tile_off, void* out_probe, bool out64, void* out_build, int64_t out_cap,
                  hipStream_t stream);
-void join_expand(const void* keys, bool key64, const uint8_t* valid, int64_t m, const int64_t* tkeys,
-                 const void* thead, const void* cstart, const void* crows, bool rid64, int64_t cap, int64_t kmin,
-                 bool direct, const int64_t* offsets, int32_t* out_probe, void* out_build, const uint32_t* bits,
-                 uint64_t bmask, int64_t out_cap, hipStream_t stream);
+void join_expand(const JoinTableRef& t, const KeyColumn& probe, bool use_filter, const int64_t* offsets,
+                 int32_t* out_probe, void* out_build, int64_t out_cap, hipStream_t stream);
 // run ids of a non-decreasing key column: gid[i] = r for rows in [starts[r], starts[r+1])
 void fill_runs(const void* starts, bool starts64, int64_t nruns, int64_t n, int32_t* gid, hipStream_t stream);
 void groupby_build(const void* keys, bool key64, int64_t n, int64_t* tkeys, int32_t* trow, int64_t cap, int64_t kmin,

@@ -11,7 +11,6 @@ from __future__ import annotations
 
 from ..utils import switches as _sw
 import contextvars
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -183,6 +182,12 @@ def _keys_ok(k: torch.Tensor) -> torch.Tensor:
     return k.contiguous()
 
 
+def _key_column(keys: torch.Tensor, valid: Optional[torch.Tensor] = None):
+    """A build or probe key column (``_keys_ok`` keys, optional validity mask)
+    as the native join entry points take it (csrc/kernels/kernels.h KeyColumn)."""
+    return native().KeyColumn(ptr(keys), keys.dtype == torch.int64, ptr(valid), keys.numel())
+
+
 class JoinTable:
     """Hash table over build-side keys (int32/int64; NULL keys never match)."""
 
@@ -247,18 +252,17 @@ class JoinTable:
         self.thead = torch.empty(self.slots, dtype=self.rid, device=self.device)
         self.tkeys = torch.empty(1 if self.direct else self.slots, dtype=torch.int64, device=self.device)
         dups = torch.empty(1, dtype=torch.int64, device=self.device)
-        k64 = keys.dtype == torch.int64
         st = stream(keys)
         # thead = -1, tkeys = EMPTY_KEY (hashed), bits = 0, dups = 0: one launch
         N.join_table_init(ptr(self.thead), self.rid64, self.slots, 0 if self.direct else ptr(self.tkeys),
                           ptr(self.bits), 0 if self.bits is None else self.bits.numel(), ptr(dups), st)
-        N.join_build(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
-                     self.kmin, self.direct, ptr(dups), ptr(self.bits), self.bmask, st)
+        self.cstart = self.crows = None
+        self._set_ref()
+        N.join_build(self._ref, _key_column(keys, valid), ptr(dups), st)
         if known_unique and CHECK_KEY_TAGS and not capturing():
             # debug / test mode: the tag-derived uniqueness must match the build's own duplicate count
             if to_host_int(dups) != 0:
                 raise AssertionError("key_unique() trusted a key tag on keys that hold duplicates")
-        self.cstart = self.crows = None
         self._csr_src = (keys, valid)
         if known_unique:
             self._unique = True
@@ -284,18 +288,24 @@ class JoinTable:
         self._unique, self._dups = u, None
         if not u:
             keys, valid = self._csr_src
-            k64 = keys.dtype == torch.int64
+            col = _key_column(keys, valid)
             st = stream(keys)
-            n = self.n
             cnt = torch.zeros(self.slots + 1, dtype=self.rid, device=self.device)
-            launch("join_csr_count").join_csr_count(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(cnt),
-                                                    self.rid64, self.cap, self.kmin, self.direct, st)
+            launch("join_csr_count").join_csr_count(self._ref, col, ptr(cnt), st)
             self.cstart = torch.zeros(self.slots + 1, dtype=self.rid, device=self.device)
             torch.cumsum(cnt[:-1], 0, dtype=self.rid, out=self.cstart[1:])
-            self.crows = torch.empty(n, dtype=self.rid, device=self.device)
-            launch("join_csr_scatter").join_csr_scatter(ptr(keys), k64, ptr(valid), n, ptr(self.tkeys), ptr(cnt),
-                                                        ptr(self.cstart), ptr(self.crows), self.rid64, self.cap,
-                                                        self.kmin, self.direct, st)
+            self.crows = torch.empty(self.n, dtype=self.rid, device=self.device)
+            self._set_ref()
+            launch("join_csr_scatter").join_csr_scatter(self._ref, col, ptr(cnt), st)
+
+    def _set_ref(self) -> None:
+        """The table as the native entry points take it (csrc/kernels/kernels.h
+        JoinTableRef): made after the build's buffers exist, and again when
+        the CSR runs or the fold scratch are added."""
+        self._ref = native().JoinTableRef(
+            tkeys=ptr(self.tkeys), thead=ptr(self.thead), cstart=ptr(self.cstart), crows=ptr(self.crows),
+            rid64=self.rid64, cap=self.cap, kmin=self.kmin, direct=self.direct, bits=ptr(self.bits),
+            bmask=self.bmask, fold=ptr(self._fold), n_build=self.n)
 
     @staticmethod
     def _direct_for(span: int, n: int) -> bool:
@@ -322,11 +332,8 @@ class JoinTable:
                 self._cpu_mark(cnt, lo, build_matched)
             return first
         first = torch.empty(m, dtype=self.rid, device=pkeys.device)
-        N = launch("join_probe")
-        bits, bmask = self._bloom(m)
-        N.join_probe(ptr(pkeys), pkeys.dtype == torch.int64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead),
-                     ptr(self.cstart), ptr(self.crows), self.rid64, self.cap, self.kmin, self.direct, 0, ptr(first),
-                     ptr(build_matched), bits, bmask, stream(pkeys))
+        launch("join_probe").join_probe(self._ref, _key_column(pkeys, pvalid), self._use_filter(m), 0, ptr(first),
+                                        ptr(build_matched), stream(pkeys))
         return first
 
     def probe_select(self, pkeys: torch.Tensor, pvalid: Optional[torch.Tensor] = None, negate: bool = False,
@@ -345,14 +352,14 @@ class JoinTable:
             return sel, (first.index_select(0, sel.long()) if want_build and not negate else None)
         N = launch("probe_hits")
         st = stream(pkeys)
-        k64 = pkeys.dtype == torch.int64
+        col = _key_column(pkeys, pvalid)
         tiles = N.probe_hit_tiles(m)
         words = torch.empty(tiles * 128, dtype=torch.int64, device=dev)
         tcount = torch.empty(tiles, dtype=torch.int64, device=dev)
-        bits, bmask = self._bloom(m)
-        fold = self._fold_scratch(m, bits, bmask, st)
-        N.probe_hits(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
-                     self.kmin, self.direct, bits, bmask, negate, self.n, fold, ptr(words), ptr(tcount), st)
+        use_filter = self._use_filter(m)
+        if use_filter:
+            self._fold_scratch(m, st)
+        N.probe_hits(self._ref, col, use_filter, negate, ptr(words), ptr(tcount), st)
         if self._unique is None:
             # deferred duplicate count: read back with the hit total (one sync);
             # duplicate build keys leave the pairs to the multi-match probe
@@ -367,8 +374,7 @@ class JoinTable:
         pidx = torch.empty(total, dtype=it, device=dev)
         bidx = torch.empty(total, dtype=self.rid, device=dev) if want_build and not negate else None
         if total:
-            N.probe_write(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), self.rid64, self.cap,
-                          self.kmin, self.direct, ptr(words), ptr(toff), ptr(pidx), it == torch.int64, ptr(bidx),
+            N.probe_write(self._ref, col, ptr(words), ptr(toff), ptr(pidx), it == torch.int64, ptr(bidx),
                           pidx.numel(), st)
         tags.INCR.set(pidx, True)    # hit rows in row order
         return pidx, bidx
@@ -401,39 +407,35 @@ class JoinTable:
         N = launch("join_probe")
         s = stream(pkeys)
         counts = torch.empty(m, dtype=torch.int32, device=dev)
-        k64 = pkeys.dtype == torch.int64
-        bits, bmask = self._bloom(m)
-        N.join_probe(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), ptr(self.cstart),
-                     ptr(self.crows), self.rid64, self.cap, self.kmin, self.direct, ptr(counts), 0,
-                     ptr(build_matched), bits, bmask, s)
+        col = _key_column(pkeys, pvalid)
+        use_filter = self._use_filter(m)
+        N.join_probe(self._ref, col, use_filter, ptr(counts), 0, ptr(build_matched), s)
         offsets, total = exclusive_scan(counts)
         pidx = torch.empty(total, dtype=torch.int32, device=dev)
         bidx = torch.empty(total, dtype=self.rid, device=dev)
         if total:
             launch("join_expand")
-            N.join_expand(ptr(pkeys), k64, ptr(pvalid), m, ptr(self.tkeys), ptr(self.thead), ptr(self.cstart),
-                          ptr(self.crows), self.rid64, self.cap, self.kmin, self.direct, ptr(offsets), ptr(pidx),
-                          ptr(bidx), bits, bmask, pidx.numel(), s)
+            N.join_expand(self._ref, col, use_filter, ptr(offsets), ptr(pidx), ptr(bidx), pidx.numel(), s)
         return pidx, bidx, counts
 
-    def _bloom(self, m: int) -> Tuple[int, int]:
+    def _use_filter(self, m: int) -> bool:
         """Use the Bloom filter only when the probe side is much larger than the
         build side (then most probes are expected to miss)."""
-        if self.bits is not None and m >= BLOOM_MIN_RATIO * self.n:
-            return ptr(self.bits), self.bmask
-        return 0, 0
+        return self.bits is not None and m >= BLOOM_MIN_RATIO * self.n
 
-    def _fold_scratch(self, m: int, bits: int, bmask: int, st: int) -> int:
+    def _bloom(self, m: int) -> Tuple[int, int]:
+        """(filter words, bmask) a probe of ``m`` rows consults; (0, 0): none."""
+        return (ptr(self.bits), self.bmask) if self._use_filter(m) else (0, 0)
+
+    def _fold_scratch(self, m: int, st: int) -> None:
         """The exact bitmap folded to the 64 KiB that probe_hits' fold kernels
         keep in LDS, for bitmaps wider than that: computed by the first probe
-        that takes one of them and kept with the table (0: not needed)."""
+        that uses the filter and takes one of them, and kept with the table."""
         N = native()
-        if not (bits and self.direct and bmask >> 63 and N.probe_fold_needed(m, self.cap)):
-            return 0
-        if self._fold is None:
+        if self._fold is None and self.direct and self.bmask >> 63 and N.probe_fold_needed(m, self.cap):
             self._fold = torch.empty(N.kFoldWords, dtype=torch.int32, device=self.device)
-            N.probe_fold_build(bits, self.cap, ptr(self._fold), st)
-        return ptr(self._fold)
+            N.probe_fold_build(ptr(self.bits), self.cap, ptr(self._fold), st)
+            self._set_ref()
 
     # ------------------------------------------------------------ cpu helpers
     def _cpu_ranges(self, pkeys, pvalid):
@@ -825,6 +827,21 @@ def _group_slots(direct: bool, cap: int) -> int:
     return cap if direct else cap + 1
 
 
+def _group_build(keys: torch.Tensor, n: int):
+    """The group-by table over ``keys`` after its build pass: (kmin, direct,
+    cap, nslots, tkeys, trow), trow[slot] = the smallest row of the slot's key
+    (INT32_MAX: an empty slot)."""
+    kmin, direct, cap = _group_table(keys, n)
+    dev = keys.device
+    nslots = _group_slots(direct, cap)
+    trow = torch.full((nslots,), INT32_MAX, dtype=torch.int32, device=dev)
+    tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
+             else torch.full((nslots,), EMPTY_KEY, dtype=torch.int64, device=dev))
+    launch("groupby").groupby_build(ptr(keys), keys.dtype == torch.int64, n, ptr(tkeys), ptr(trow), cap, kmin,
+                                    direct, stream(keys))
+    return kmin, direct, cap, nslots, tkeys, trow
+
+
 def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
     """Dense group ids for int keys (no NULLs: callers map NULL to a reserved key).
 
@@ -840,15 +857,9 @@ def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
         g = uniq.numel()
         rep = torch.full((g,), n, dtype=torch.int64).scatter_reduce(0, inv, torch.arange(n), reduce="amin")
         return inv.to(torch.int32), g, rep.to(torch.int32)
-    kmin, direct, cap = _group_table(keys, n)
-    N = launch("groupby")
+    kmin, direct, cap, nslots, tkeys, trow = _group_build(keys, n)
+    N = native()
     s = stream(keys)
-    k64 = keys.dtype == torch.int64
-    nslots = _group_slots(direct, cap)
-    trow = torch.full((nslots,), INT32_MAX, dtype=torch.int32, device=dev)
-    tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
-             else torch.full((nslots,), EMPTY_KEY, dtype=torch.int64, device=dev))
-    N.groupby_build(ptr(keys), k64, n, ptr(tkeys), ptr(trow), cap, kmin, direct, s)
     occ = torch.empty(nslots, dtype=torch.bool, device=dev)
     gid_of_slot = torch.empty(nslots, dtype=torch.int32, device=dev)
     N.groupby_occupied(ptr(trow), nslots, ptr(occ), ptr(gid_of_slot), s)
@@ -857,7 +868,7 @@ def group_ids(keys: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
     rep = torch.empty(g, dtype=torch.int32, device=dev)
     N.groupby_assign(ptr(slots), slots.dtype == torch.int64, g, nslots, ptr(trow), ptr(gid_of_slot), ptr(rep), s)
     gid = torch.empty(n, dtype=torch.int32, device=dev)
-    N.groupby_lookup(ptr(keys), k64, n, ptr(tkeys), ptr(gid_of_slot), cap, kmin, direct, ptr(gid), s)
+    N.groupby_lookup(ptr(keys), keys.dtype == torch.int64, n, ptr(tkeys), ptr(gid_of_slot), cap, kmin, direct, ptr(gid), s)
     if not direct and g > 1:
         # hashed slots depend on the order in which threads inserted colliding
         # keys, so slot-order ids differ between runs; renumber the groups by
@@ -893,16 +904,9 @@ def first_rows_mask(keys: torch.Tensor) -> torch.Tensor:
             _, _, rep = group_ids(keys)
             mark[rep.long()] = True
         return mark
-    kmin, direct, cap = _group_table(keys, n)
-    s = stream(keys)
-    nslots = _group_slots(direct, cap)
-    trow = torch.full((nslots,), INT32_MAX, dtype=torch.int32, device=dev)
-    tkeys = (torch.empty(1, dtype=torch.int64, device=dev) if direct
-             else torch.full((nslots,), EMPTY_KEY, dtype=torch.int64, device=dev))
-    launch("groupby").groupby_build(ptr(keys), keys.dtype == torch.int64, n, ptr(tkeys), ptr(trow), cap, kmin,
-                                    direct, s)
+    _, _, _, nslots, _, trow = _group_build(keys, n)
     mark = torch.zeros(n, dtype=torch.bool, device=dev)
-    launch("mark_slot_rows").mark_slot_rows(ptr(trow), nslots, n, ptr(mark), s)
+    launch("mark_slot_rows").mark_slot_rows(ptr(trow), nslots, n, ptr(mark), stream(keys))
     return mark
 
 

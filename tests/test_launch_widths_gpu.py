@@ -59,15 +59,12 @@ def _probe_write_native(t, pk, out_dt):
     tiles = N.probe_hit_tiles(m)
     words = torch.empty(tiles * 128, dtype=torch.int64, device=dev)
     tcount = torch.empty(tiles, dtype=torch.int64, device=dev)
-    k64 = pk.dtype == torch.int64
-    bits, bmask = t._bloom(m)
-    N.probe_hits(ptr(pk), k64, 0, m, ptr(t.tkeys), ptr(t.thead), t.rid64, t.cap, t.kmin, t.direct, bits, bmask, False,
-                 t.n, 0, ptr(words), ptr(tcount), st)
+    col = N.KeyColumn(ptr(pk), pk.dtype == torch.int64, 0, m)
+    N.probe_hits(t._ref, col, t._use_filter(m), False, ptr(words), ptr(tcount), st)
     toff, total = exclusive_scan(tcount)
     pidx = torch.full((total,), -7, dtype=out_dt, device=dev)
     bidx = torch.full((total,), -7, dtype=t.rid, device=dev)
-    N.probe_write(ptr(pk), k64, 0, m, ptr(t.tkeys), ptr(t.thead), t.rid64, t.cap, t.kmin, t.direct, ptr(words),
-                  ptr(toff), ptr(pidx), out_dt == torch.int64, ptr(bidx), total, st)
+    N.probe_write(t._ref, col, ptr(words), ptr(toff), ptr(pidx), out_dt == torch.int64, ptr(bidx), total, st)
     _sync()
     return pidx, bidx
 
@@ -135,6 +132,37 @@ def test_join_table_key_and_row_id_widths(gpu_device, monkeypatch, key_dt, dense
     hits = mask_to_indices(rc > 0).long()
     assert torch.equal(p32.cpu().long(), hits) and torch.equal(p64.cpu(), hits)
     assert torch.equal(b32, b64) and torch.equal(bk[b64.cpu().long()], pk[hits])
+
+
+@pytest.mark.parametrize("use_filter", [True, False])
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("key_dt", INTS)
+def test_probe_first_direct_ragged_tails(gpu_device, monkeypatch, key_dt, masked, use_filter):
+    """JoinTable.probe_first on a direct unique table (the 4-rows-per-lane
+    first-match kernel, which batches its loads through probe_heads) against
+    the CPU JoinTable: row counts around the 4-row batch and the 256-lane
+    workgroup, with and without a validity mask, with the exact bitmap
+    consulted (ratio 0: at every row count; the last count also under the real
+    ratio) and not consulted (a ratio no probe reaches)."""
+    r = np.random.default_rng(23)
+    lo = 10**12 if key_dt == torch.int64 else -300
+    bk = torch.from_numpy(r.choice(np.arange(lo, lo + 1100), NB, replace=False)).to(key_dt)
+    cpu = H.JoinTable(bk)
+    gpu = H.JoinTable(bk.to(gpu_device))
+    assert gpu.direct and gpu.unique and gpu.cstart is None and gpu.bmask >> 63
+    real = H.BLOOM_MIN_RATIO * NB + 1       # a probe the unpatched rule filters
+    for m in (1, 3, 4, 5, 1023, 1024, 1025, 4 * 256 * 2 + 1, real):
+        pk = torch.from_numpy(r.integers(lo - 50, lo + 1150, m)).to(key_dt)
+        pv = torch.from_numpy(r.random(m) < 0.7) if masked else None
+        want = cpu.probe_first(pk, pv)
+        with monkeypatch.context() as mp:
+            if not use_filter:
+                mp.setattr(H, "BLOOM_MIN_RATIO", 2**40)
+            elif m != real:
+                mp.setattr(H, "BLOOM_MIN_RATIO", 0)
+            assert gpu._use_filter(m) == use_filter
+            got = gpu.probe_first(pk.to(gpu_device), None if pv is None else pv.to(gpu_device))
+        assert got.dtype == torch.int32 and torch.equal(got.cpu(), want), m
 
 
 # ------------------------------------------------------------------ sorted ranges

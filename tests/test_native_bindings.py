@@ -71,6 +71,60 @@ def test_signature_arity_and_return(name):
         assert "arg1: bool, arg2: " in doc
 
 
+# ---- join tables: one JoinTableRef and one KeyColumn per call, through the same adaptor
+TABLE = dict(tkeys=16, thead=32, rid64=False, cap=8, kmin=0, direct=False, n_build=4)
+# name -> arguments after (table, key column); the stream comes last
+JOIN_ENTRY = {
+    "join_build": [64, 0],                               # dups
+    "join_csr_count": [64, 0],                           # cnt
+    "join_csr_scatter": [64, 0],                         # cnt
+    "join_probe": [False, 0, 64, 0, 0],                  # use_filter, counts, first, build_matched
+    "probe_hits": [False, False, 64, 64, 0],             # use_filter, negate, words, tile_counts
+    "probe_write": [64, 64, 64, False, 0, 0, 0],         # words, tile_off, out_probe, out64, out_build, out_cap
+    "join_expand": [False, 64, 64, 64, 0, 0],            # use_filter, offsets, out_probe, out_build, out_cap
+}
+
+
+def _table(**over):
+    return native().JoinTableRef(**{**TABLE, **over})
+
+
+@pytest.mark.parametrize("field", ["tkeys", "thead", "cstart", "crows", "bits", "fold"])
+@pytest.mark.parametrize("bad", ["0", -1])
+def test_table_ref_pointer_conversion(field, bad):
+    with pytest.raises(TypeError):
+        _table(**{field: bad})
+
+
+def test_table_ref_fields_go_by_name():
+    with pytest.raises(TypeError):
+        native().JoinTableRef(16, 32, 0, 0, False, 8, 0, False, 0, 0, 0, 4)
+    with pytest.raises(TypeError):
+        native().KeyColumn("0", False, 0, 1)
+    with pytest.raises(TypeError):
+        native().KeyColumn(-1, False, 0, 1)
+
+
+@pytest.mark.parametrize("name", sorted(JOIN_ENTRY))
+@pytest.mark.parametrize("over", [dict(tkeys=0), dict(thead=0), dict(cstart=48), dict(crows=48)],
+                         ids=["hashed-no-tkeys", "no-thead", "cstart-only", "crows-only"])
+def test_table_check_refuses_before_any_launch(name, over):
+    # m > 0 and a non-null dummy key pointer: the table check comes first, nothing is dereferenced or launched
+    col = native().KeyColumn(64, False, 0, 5)
+    with pytest.raises(RuntimeError, match=name + ": null buffer"):
+        getattr(native(), name)(_table(**over), col, *JOIN_ENTRY[name])
+
+
+@pytest.mark.parametrize("name", sorted(JOIN_ENTRY))
+def test_join_entry_points_take_the_adaptor_shape(name):
+    doc = getattr(native(), name).__doc__
+    assert doc.startswith(name + "(arg0: ")
+    assert "arg0: igloo_amd._native.JoinTableRef, arg1: igloo_amd._native.KeyColumn, arg2: " in doc
+    assert doc.count("arg") == 2 + len(JOIN_ENTRY[name]) and "-> None" in doc
+    with pytest.raises(TypeError):      # a str for the stream, as for every adapted launcher
+        getattr(native(), name)(_table(), native().KeyColumn(64, False, 0, 0), *JOIN_ENTRY[name][:-1], "0")
+
+
 def test_guarded_binding_still_checks():
     # hand-written binding: null buffers with cap > 0 are refused before the launch
     with pytest.raises(RuntimeError, match="probe_fold_build: null buffer"):
