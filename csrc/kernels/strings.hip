@@ -110,7 +110,12 @@ __global__ __launch_bounds__(kBlock) void like_tile_kernel(const int64_t* __rest
 
 // LIKE over '%'-separated literal segments (no '_', case-sensitive) — the
 // shape of nearly every analytic LIKE: 'PROMO%', '%BRASS', '%green%',
-// '%special%requests%'. Per tile of 256 strings staged in LDS:
+// '%special%requests%'. Two kernels (str_like_segments routes):
+//   * like_stream_kernel, further down: 1-2 segments of >= 7 bytes each. The
+//     column is scanned as one byte stream and rows are looked at only where
+//     an aligned dword of the longest segment shows up;
+//   * like_seg_kernel, here: everything else (short segments, 3-4 segments).
+// like_seg_kernel, per tile of 256 strings staged in LDS:
 //   1. every lane takes 16-byte chunks of the tile and marks, for every
 //      segment, the positions where it starts: 4-byte windows built with
 //      v_alignbyte from five dwords are compared against the segment prefix in
@@ -170,7 +175,30 @@ __device__ inline bool seg_walk(const uint64_t (&bits)[SEGS][WORDS], const int32
   return r;
 }
 
-// oversized tile: literal-by-literal search of one string in global memory
+// unaligned loads (global memory takes any alignment; one instruction each)
+__device__ inline uint32_t load_u32(const uint8_t* p) {
+  uint32_t x;
+  __builtin_memcpy(&x, p, 4);
+  return x;
+}
+__device__ inline uint4 load_u128(const uint8_t* p) {
+  uint4 x;
+  __builtin_memcpy(&x, p, 16);
+  return x;
+}
+
+// The exact matcher on one string s[0, L) in global memory, literal by
+// literal: the leftmost occurrence of each segment after the previous one.
+// Never reads outside the string.
+// kDword = false: byte by byte, any segment length. Every byte is a load
+// that depends on the one before, so this is for the rare oversized tile.
+// kDword = true, every segment >= 7 bytes: a few rounds of independent loads
+// per string. An occurrence at p contains, for any 4-byte grid, the grid's
+// dword at p rounded up, which equals the segment's bytes at 0..3 + (0..3);
+// so 16-byte pieces of the string (four at a time, the last one read
+// overlapping so that it ends at L) are tested dword by dword against those
+// four windows and only a hit is compared in full, with dword loads.
+template <bool kDword>
 __device__ inline bool seg_search(const uint8_t* s, int64_t L, const uint8_t* sseg, const int32_t* soff, int nseg,
                                   bool anchor_start, bool anchor_end) {
   int64_t cur = 0;
@@ -178,10 +206,82 @@ __device__ inline bool seg_search(const uint8_t* s, int64_t L, const uint8_t* ss
   for (int sg = 0; sg < nseg && r; ++sg) {
     const int s0 = soff[sg], sl = soff[sg + 1] - s0;
     const bool last = sg == nseg - 1;
-    auto eq = [&](int64_t p) {
-      for (int k = 0; k < sl; ++k)
-        if (s[p + k] != sseg[s0 + k]) return false;
-      return true;
+    auto seg_u32 = [&](int k) {
+      return (uint32_t)sseg[s0 + k] | ((uint32_t)sseg[s0 + k + 1] << 8) | ((uint32_t)sseg[s0 + k + 2] << 16) |
+             ((uint32_t)sseg[s0 + k + 3] << 24);
+    };
+    auto eq = [&](int64_t p) {   // p + sl <= L
+      if constexpr (kDword) {
+        // dwords at 0, 4, 8, 12 (the last one moved back to end at sl): loads that do not wait for each other
+        uint32_t diff = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k += 4) {
+          const int o = k < sl - 4 ? k : sl - 4;
+          diff |= load_u32(s + p + o) ^ seg_u32(o);
+        }
+        for (int k = 16; k < sl && !diff; k += 4) {
+          const int o = k < sl - 4 ? k : sl - 4;
+          diff |= load_u32(s + p + o) ^ seg_u32(o);
+        }
+        return diff == 0;
+      } else {
+        for (int k = 0; k < sl; ++k)
+          if (s[p + k] != sseg[s0 + k]) return false;
+        return true;
+      }
+    };
+    // smallest p >= from with p + sl <= L where the segment occurs, or -1
+    auto find = [&](int64_t from) -> int64_t {
+      if constexpr (kDword) {
+        if (from + sl > L) return -1;
+        const uint32_t W[4] = {seg_u32(0), seg_u32(1), seg_u32(2), seg_u32(3)};
+        // the piece at string position c: occurrences whose grid dword it holds, in ascending order
+        auto scan = [&](const uint4& v, int64_t c) -> int64_t {
+          uint32_t m = ~0u;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) m = min(min(m, v.x ^ W[o]), min(min(v.y ^ W[o], v.z ^ W[o]), v.w ^ W[o]));
+          if (m) return -1;
+          const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+          uint32_t hits = 0;   // bit 4 w + 3 - o: dword w equals window o, i.e. a start at c + 4 w - o
+#pragma unroll
+          for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int o = 0; o < 4; ++o) hits |= (uint32_t)(d[w] == W[o]) << (4 * w + 3 - o);
+          for (; hits; hits &= hits - 1) {
+            const int64_t p = c + __builtin_ctz(hits) - 3;   // ascending
+            if (p >= from && p + sl <= L && eq(p)) return p;
+          }
+          return -1;
+        };
+        if (L < 16) {   // one zero-filled piece holds the string
+          uint32_t d[4] = {0, 0, 0, 0};
+          for (int k = 0; k < (int)L; ++k) d[k >> 2] |= (uint32_t)s[k] << (8 * (k & 3));
+          return scan(uint4{d[0], d[1], d[2], d[3]}, 0);
+        }
+        // pieces on the grid of the string's start; one that would pass the
+        // end is read at L - 16 instead: on its own grid it still holds a
+        // dword of every occurrence not seen in the pieces before it
+        for (int64_t c = from & ~(int64_t)15; c < L; c += 64) {
+          int64_t cc[4];
+          uint4 v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            cc[u] = c + 16 * u < L - 16 ? c + 16 * u : L - 16;
+            v[u] = load_u128(s + cc[u]);
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (u && c + 16 * u >= L) break;
+            const int64_t p = scan(v[u], cc[u]);
+            if (p >= 0) return p;
+          }
+        }
+        return -1;
+      } else {
+        int64_t p = from;
+        while (p + sl <= L && !eq(p)) ++p;
+        return p + sl <= L ? p : -1;
+      }
     };
     if (sg == 0 && anchor_start) {
       r = cur + sl <= L && eq(cur);
@@ -190,9 +290,8 @@ __device__ inline bool seg_search(const uint8_t* s, int64_t L, const uint8_t* ss
       r = L - sl >= cur && eq(L - sl);
       cur = L;
     } else {
-      int64_t p = cur;
-      while (p + sl <= L && !eq(p)) ++p;
-      r = p + sl <= L;
+      const int64_t p = find(cur);
+      r = p >= 0;
       cur = p + sl;
     }
   }
@@ -277,187 +376,223 @@ __global__ __launch_bounds__(BLOCK) void like_seg_kernel(const int64_t* __restri
       const int64_t a = off[i], e = off[i + 1];
       const bool r = staged ? seg_walk(bits, soff, nseg, anchor_start, anchor_end,
                                        (int)((uintptr_t)(chars + a) - start), (int)((uintptr_t)(chars + e) - start))
-                            : seg_search(chars + a, e - a, sseg, soff, nseg, anchor_start, anchor_end);
+                            : seg_search<false>(chars + a, e - a, sseg, soff, nseg, anchor_start, anchor_end);
       out[i] = r != negate;
     }
   }
 }
 
 // Segments of >= 7 bytes ('%special%requests%', '%Customer%Complaints%'):
-// every occurrence at position p contains the aligned dword at a = p rounded
-// up to 4, and that dword equals the segment's bytes a-p .. a-p+3 (a-p < 4,
-// a-p+3 <= 6 < length). So the positions p of a 16-byte chunk can only hold a
-// hit if one of the chunk's 5 aligned dwords equals one of the segment's 4
-// leading dword windows: 16 plain compares per chunk and segment, no byte
-// windows -- the byte-exact test (v_alignbyte windows + verification) runs
-// only for the chunks that pass, gathered into a per-wave LDS list so the
-// wave runs them densely instead of idling lanes on a divergent branch.
-// Chunks come straight from global memory (16-byte loads, the fifth dword
-// from the same lines); LDS holds only the hit bitmaps and the lists.
-constexpr int kLikeDwordTile = 32768;
+// the column is scanned as one byte stream and row structure is touched only
+// where a candidate appears.
+//
+// Prefilter. Every occurrence of a segment at position p contains the aligned
+// dword at a = p rounded up to 4, and that dword equals the segment's bytes
+// a-p .. a-p+3 (a-p < 4, a-p+3 <= 6 < length). So a row can only match if one
+// of its aligned dwords equals one of the 4 leading dword windows of a
+// segment, and since every match contains every segment, testing the longest
+// one is enough: 16 plain compares per 16-byte chunk. The row that holds an
+// occurrence holds that dword, so the rows that intersect a passing chunk are
+// the only ones that can match.
+//
+// A workgroup takes tiles of kLikeStreamRows consecutive rows. Per tile it
+// reads the two offsets that bound the tile's bytes (one tile ahead), then
+//   1. scans the 16-byte aligned chunks covering those bytes straight from
+//      global memory, kLikeStreamChunks loads per lane in flight, no LDS
+//      staging, no barrier, no limit on the tile's bytes; a lane whose chunk
+//      passes appends the chunk's index to an LDS list;
+//   2. resolves each listed chunk: the first of the tile's rows that
+//      intersects it (from the offsets of every 64th row, kept in LDS, and two
+//      rounds of independent loads), then the exact matcher (seg_search<true>:
+//      greedy order, both anchors, a few rounds of wide loads per row) on that
+//      row and the following ones that start inside the chunk; a match sets
+//      the row's bit in an LDS bitmap. When the list overflows, every row of
+//      the tile goes through the exact matcher instead: correct for any
+//      input, fast for the usual one where candidates are rare;
+//   3. writes out[i] = bit != negate for the tile's rows, 32 per lane.
+// The kernel is left at the registers it asks for (about 107 VGPRs, 4 waves
+// per SIMD): held to 8 waves it reloads spills inside the scan loop, and
+// fewer resident waves also stream faster (profiles/like_stream_ab.txt, where
+// the other tile sizes, load depths and a double-buffered scan are recorded).
+// The first chunk of a tile is aligned down and the last one runs past the
+// tile's end, so neighbouring tiles scan a shared chunk twice, but a
+// workgroup resolves and writes only rows of its own tile, each exactly once.
+// Nothing survives the launch and workgroups do not communicate.
+constexpr int kLikeStreamRows = 4096;    // rows per tile: a multiple of 32
+constexpr int kLikeStreamChunks = 4;     // 16-byte loads per lane in flight
+constexpr int kLikeStreamStep = 64;      // rows between the offsets sampled into LDS for the resolve
+static_assert(kLikeStreamRows % 32 == 0 && kLikeStreamRows / kLikeStreamStep <= kBlock, "tile shape");
+constexpr int kLikeStreamCand = 2048;    // listed chunks per tile; with more (over one per two rows) the tile takes every row
 
-template <int SEGS, int TILE, int kU>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void like_dword_kernel(const int64_t* __restrict__ off,
-                                                           const uint8_t* __restrict__ chars, int64_t n,
-                                                           const uint8_t* __restrict__ seg, const int32_t* seg_off,
-                                                           int nseg, bool anchor_start, bool anchor_end, bool negate,
-                                                           uint8_t* __restrict__ out, int64_t nbytes) {
-  constexpr int kWords = TILE / 64;
-  constexpr int kChunks = TILE / 16;
-  constexpr int kListLen = kChunks / kWavesPerBlock + kWave;
-  __shared__ uint64_t bits[SEGS][kWords];
-  __shared__ uint16_t cand[kWavesPerBlock][kListLen];
-  constexpr int kDataCap = 64;   // listed chunks whose bytes are kept in LDS (later ones are reloaded)
-  __shared__ uint32_t cdat[kWavesPerBlock][5][kDataCap];
+template <int kU>
+__global__ __launch_bounds__(kBlock) void like_stream_kernel(const int64_t* __restrict__ off,
+                                                            const uint8_t* __restrict__ chars, int64_t n,
+                                                            const uint8_t* __restrict__ seg, const int32_t* seg_off,
+                                                            int nseg, bool anchor_start, bool anchor_end, bool negate,
+                                                            uint8_t* __restrict__ out, int64_t nbytes) {
+  constexpr int R = kLikeStreamRows;
+  __shared__ uint32_t cand[kLikeStreamCand];
+  __shared__ uint32_t hit[R / 32];
+  __shared__ uint32_t ncand[2];   // by tile parity: reset two barriers before its next use
+  __shared__ int64_t samp[R / kLikeStreamStep];   // the offset of every 64th row of the tile
   __shared__ uint8_t sseg[kLikeMaxPattern];
-  __shared__ int32_t soff[SEGS + 1];
+  __shared__ int32_t soff[kSegMax + 1];
+  const int tid = threadIdx.x;
   const int total = seg_off[nseg];
-  for (int i = threadIdx.x; i < total; i += kBlock) sseg[i] = seg[i];
-  if (threadIdx.x <= nseg) soff[threadIdx.x] = seg_off[threadIdx.x];
+  for (int i = tid; i < total; i += kBlock) sseg[i] = seg[i];
+  if (tid <= nseg) soff[tid] = seg_off[tid];
+  for (int w = tid; w < R / 32; w += kBlock) hit[w] = 0;
+  if (tid < 2) ncand[tid] = 0;
   __syncthreads();
-  uint32_t P[SEGS][4];
-#pragma unroll
-  for (int sg = 0; sg < SEGS; ++sg)
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      const int s0 = soff[sg < nseg ? sg : 0] + o;
-      // wave-uniform: kept in scalar registers (compares take an SGPR operand)
-      P[sg][o] = __builtin_amdgcn_readfirstlane((uint32_t)sseg[s0] | ((uint32_t)sseg[s0 + 1] << 8) |
-                                                ((uint32_t)sseg[s0 + 2] << 16) | ((uint32_t)sseg[s0 + 3] << 24));
+  // the 4 leading dword windows of the longest segment, wave-uniform: kept in
+  // scalar registers (compares take an SGPR operand)
+  int f0 = soff[0];
+  for (int sg = 1, best = soff[1] - soff[0]; sg < nseg; ++sg)
+    if (soff[sg + 1] - soff[sg] > best) {
+      best = soff[sg + 1] - soff[sg];
+      f0 = soff[sg];
     }
-  const int wave = threadIdx.x / kWave, lane = lane_id();
-  const int64_t tiles = (n + kBlock - 1) / kBlock;
+  uint32_t P[4];
+#pragma unroll
+  for (int o = 0; o < 4; ++o)
+    P[o] = __builtin_amdgcn_readfirstlane((uint32_t)sseg[f0 + o] | ((uint32_t)sseg[f0 + o + 1] << 8) |
+                                          ((uint32_t)sseg[f0 + o + 2] << 16) | ((uint32_t)sseg[f0 + o + 3] << 24));
+  // some dword equals some window <=> the smallest of the 16 xors is 0
+  // (v_xor + v_min3: no per-compare mask bookkeeping)
+  auto passes = [&](const uint4& v) {
+    uint32_t m = ~0u;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) m = min(min(m, v.x ^ P[o]), min(min(v.y ^ P[o], v.z ^ P[o]), v.w ^ P[o]));
+    return m == 0;
+  };
   const uint8_t* const chars_end = chars + nbytes;
+  const bool out16 = ((uintptr_t)out & 15) == 0;
+  const uint32_t flip = negate ? 0x01010101u : 0u;
+  const int64_t tiles = (n + R - 1) / R;
   // the tile's byte range is known one tile ahead (no offsets -> chars load chain)
   int64_t t_lo = 0, t_hi = 0;
   if ((int64_t)blockIdx.x < tiles) {
-    const int64_t f0 = (int64_t)blockIdx.x * kBlock;
-    t_lo = off[f0];
-    t_hi = off[f0 + kBlock < n ? f0 + kBlock : n];
+    const int64_t r0 = (int64_t)blockIdx.x * R;
+    t_lo = off[r0];
+    t_hi = off[r0 + R < n ? r0 + R : n];
   }
-  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const int64_t i0 = t * kBlock;
-    const int64_t i1 = i0 + kBlock < n ? i0 + kBlock : n;
-    const int64_t i = i0 + threadIdx.x;
-    // this row's bounds now: their loads overlap the tile's matching
-    const int64_t ra = i < i1 ? off[i] : 0, re = i < i1 ? off[i + 1] : 0;
-    const uintptr_t lo = (uintptr_t)(chars + t_lo);
-    const uintptr_t hi = (uintptr_t)(chars + t_hi);
+  int par = 0;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x, par ^= 1) {
+    const int64_t i0 = t * R;
+    const int64_t i1 = i0 + R < n ? i0 + R : n;
+    const int64_t lo = t_lo, hi = t_hi;
     {
       const int64_t tn = t + gridDim.x;
       if (tn < tiles) {
-        const int64_t f0 = tn * kBlock;
-        t_lo = off[f0];
-        t_hi = off[f0 + kBlock < n ? f0 + kBlock : n];
+        const int64_t r0 = tn * R;
+        t_lo = off[r0];
+        t_hi = off[r0 + R < n ? r0 + R : n];
       }
     }
-    const uintptr_t start = lo & ~(uintptr_t)15;   // never below the allocation (>= 256 B aligned)
-    const int len = (int)(hi - start);
-    const bool fits = hi - start <= (uintptr_t)TILE;
-    const uint8_t* base = (const uint8_t*)start;
-    // 20 bytes from chunk j (16 B and the next dword). Bytes past the tile
-    // are the next rows' (positions that would need them are masked by
-    // `room`); only the buffer's last bytes are read one by one.
-    const int64_t avail = chars_end - base;
-    auto load = [&](int j, uint32_t d[5]) {
-      const int b = j * 16;
-      if (b + 20 <= avail) {
-        const uint4 v = *(const uint4*)(base + b);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        d[4] = *(const uint32_t*)(base + b + 16);
-      } else {
+    // chunk j is the 16 bytes at position pos0 + 16 j of the buffer, 16-byte aligned in memory
+    const int64_t pos0 = lo - (int64_t)((uintptr_t)(chars + lo) & 15);
+    const int64_t nchunks = hi > lo ? (hi - pos0 + 15) >> 4 : 0;
+    // chunks [jv0, jv1) lie wholly inside the buffer; the others (at most the
+    // first and the last) are read byte by byte, never outside [chars, chars_end)
+    const int64_t jv0 = pos0 < 0 ? 1 : 0;
+    const int64_t jv1 = (nbytes - pos0) >> 4;
+    const bool listed = nchunks <= 0xffffffffLL;   // chunk indices are kept in 32 bits
+    // sampled offsets for the resolve: loaded now, needed only after the scan
+    const bool sampler = i0 + (int64_t)tid * kLikeStreamStep < i1 && tid < R / kLikeStreamStep;
+    const int64_t sample = sampler ? off[i0 + (int64_t)tid * kLikeStreamStep] : 0;
+    auto load = [&](int64_t j) {
+      if (j >= jv0 && j < jv1) return *(const uint4*)(chars + (pos0 + 16 * j));
+      uint32_t d[4];
 #pragma unroll
-        for (int w = 0; w < 5; ++w) {
-          uint32_t x = 0;
+      for (int w = 0; w < 4; ++w) {
+        uint32_t x = 0;
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (b + 4 * w + k < avail) x |= (uint32_t)base[b + 4 * w + k] << (8 * k);
-          d[w] = x;
+        for (int k = 0; k < 4; ++k) {
+          const uint8_t* p = chars + (pos0 + 16 * j + 4 * w + k);
+          if (p >= chars && p < chars_end) x |= (uint32_t)*p << (8 * k);
         }
+        d[w] = x;
       }
+      return uint4{d[0], d[1], d[2], d[3]};
     };
-    __syncthreads();   // the previous tile's walk is done with the bitmaps
-    if (fits) {
-      const int nchunks = (len + 15) >> 4;
-      int ncand = 0;
-      // kU chunks per lane in flight: all loads issued before any compare
-      for (int j0 = wave * kWave; j0 < nchunks; j0 += kU * kBlock) {
-        uint32_t d[kU][5];
+    auto append = [&](int64_t j) {
+      const uint32_t c = atomicAdd(&ncand[par], 1u);
+      if (c < (uint32_t)kLikeStreamCand) cand[c] = (uint32_t)j;
+    };
+    if (listed) {
+      for (int64_t j0 = 0; j0 < nchunks; j0 += kU * kBlock) {
+        uint4 v[kU];
+        if (j0 >= jv0 && j0 + kU * kBlock <= (nchunks < jv1 ? nchunks : jv1)) {   // uniform: all loads, then all compares
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-          const int j = j0 + u * kBlock + lane;
-          if (j < nchunks) load(j, d[u]);
-        }
+          for (int u = 0; u < kU; ++u) v[u] = *(const uint4*)(chars + (pos0 + 16 * (j0 + u * kBlock + tid)));
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-          const int j = j0 + u * kBlock + lane;
-          if (j0 + u * kBlock >= nchunks) break;   // wave-uniform
-          bool any = false;
-          if (j < nchunks) {
-#pragma unroll
-            for (int sg = 0; sg < SEGS; ++sg) {
-              if (sg >= nseg) break;
-              bool f = d[u][0] == P[sg][0];
-#pragma unroll
-              for (int w = 1; w < 4; ++w)
-                f |= (d[u][w] == P[sg][0]) | (d[u][w] == P[sg][1]) | (d[u][w] == P[sg][2]) | (d[u][w] == P[sg][3]);
-              f |= (d[u][4] == P[sg][1]) | (d[u][4] == P[sg][2]) | (d[u][4] == P[sg][3]);
-              any |= f;
-              ((uint16_t*)bits[sg])[j] = 0;
-            }
-          }
-          const uint64_t bal = __ballot(any);
-          if (any) {
-            const int c = ncand + lane_prefix(bal);
-            cand[wave][c] = (uint16_t)j;
-            if (c < kDataCap)
-#pragma unroll
-              for (int w = 0; w < 5; ++w) cdat[wave][w][c] = d[u][w];
-          }
-          ncand += __popcll(bal);
-        }
-      }
-      // byte-exact masks for the listed chunks (same wave: ordered after the zeroing)
-      for (int c = lane; c < ncand; c += kWave) {
-        const int j = cand[wave][c];
-        uint32_t d[5];
-        if (c < kDataCap) {
-#pragma unroll
-          for (int w = 0; w < 5; ++w) d[w] = cdat[wave][w][c];
+          for (int u = 0; u < kU; ++u)
+            if (passes(v[u])) append(j0 + u * kBlock + tid);
         } else {
-          load(j, d);
-        }
-        const int b = j * 16;
 #pragma unroll
-        for (int sg = 0; sg < SEGS; ++sg) {
-          if (sg >= nseg) break;
-          const int s0 = soff[sg], sl = soff[sg + 1] - s0;
-          uint32_t m = 0;
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const uint32_t w = __builtin_amdgcn_alignbyte(d[(q >> 2) + 1], d[q >> 2], q & 3);
-            m |= (uint32_t)(w == P[sg][0]) << q;
+          for (int u = 0; u < kU; ++u) {
+            const int64_t j = j0 + u * kBlock + tid;
+            if (j < nchunks && passes(load(j))) append(j);
           }
-          const int room = len - sl - b + 1;
-          m &= room >= 16 ? 0xffffu : room <= 0 ? 0u : ((1u << room) - 1);
-          for (uint32_t c2 = m; c2; c2 &= c2 - 1) {
-            const int q = __builtin_ctz(c2);
-            for (int k = 4; k < sl; ++k)
-              if (base[b + q + k] != sseg[s0 + k]) {
-                m &= ~(1u << q);
-                break;
-              }
-          }
-          ((uint16_t*)bits[sg])[j] = (uint16_t)m;
         }
       }
+    }
+    if (sampler) samp[tid] = sample;
+    __syncthreads();
+    auto test_row = [&](int64_t r) {
+      const int64_t a = off[r], e = off[r + 1];
+      if (seg_search<true>(chars + a, e - a, sseg, soff, nseg, anchor_start, anchor_end))
+        atomicOr(&hit[(r - i0) >> 5], 1u << ((r - i0) & 31));
+    };
+    const uint32_t nc = ncand[par];
+    if (listed && nc <= (uint32_t)kLikeStreamCand) {
+      for (uint32_t c = tid; c < nc; c += kBlock) {
+        const int64_t b = pos0 + 16 * (int64_t)cand[c];
+        const int64_t first = b > lo ? b : lo;              // in [lo, hi): the chunk intersects the tile
+        const int64_t end = b + 16 < hi ? b + 16 : hi;
+        // the last row of the tile that starts at or before `first` holds that
+        // byte (rows before it that start there too are empty). Every load of
+        // an offset waits a full trip through a busy memory system, so: the
+        // group of 64 rows from the samples in LDS, then two rounds of seven
+        // loads that do not wait for each other (every 8th row, then every
+        // row). Offsets past the group are larger than `first` already; off[i1] is.
+        int k = 0, ke = (int)((i1 - i0 + kLikeStreamStep - 1) / kLikeStreamStep);
+        while (ke - k > 1) {
+          const int mid = (k + ke) >> 1;
+          if (samp[mid] <= first) k = mid;
+          else ke = mid;
+        }
+        int64_t r = i0 + (int64_t)k * kLikeStreamStep;
+#pragma unroll
+        for (int step = 8; step; step >>= 3) {
+          int64_t x[7];
+#pragma unroll
+          for (int q = 0; q < 7; ++q) x[q] = off[r + (q + 1) * step < i1 ? r + (q + 1) * step : i1];
+          int cnt = 0;
+#pragma unroll
+          for (int q = 0; q < 7; ++q) cnt += x[q] <= first;
+          r += cnt * step;
+        }
+        for (; r < i1 && off[r] < end; ++r) test_row(r);
+      }
+    } else {
+      for (int64_t r = i0 + tid; r < i1; r += kBlock) test_row(r);
     }
     __syncthreads();
-    if (i < i1) {
-      const bool r = fits ? seg_walk(bits, soff, nseg, anchor_start, anchor_end,
-                                     (int)((uintptr_t)(chars + ra) - start), (int)((uintptr_t)(chars + re) - start))
-                          : seg_search(chars + ra, re - ra, sseg, soff, nseg, anchor_start, anchor_end);
-      out[i] = r != negate;
+    if (tid == 0) ncand[par] = 0;
+    for (int w = tid; w < R / 32; w += kBlock) {
+      const uint32_t bits = hit[w];
+      if (bits) hit[w] = 0;
+      const int64_t r0 = i0 + 32 * w;
+      if (out16 && r0 + 32 <= i1) {
+        uint32_t d[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) d[q] = ((((bits >> (4 * q)) & 15u) * 0x00204081u) & 0x01010101u) ^ flip;   // 4 bits -> 4 bytes
+        *(uint4*)(out + r0) = uint4{d[0], d[1], d[2], d[3]};
+        *(uint4*)(out + r0 + 16) = uint4{d[4], d[5], d[6], d[7]};
+      } else {
+        for (int k = 0; k < 32 && r0 + k < i1; ++k) out[r0 + k] = (uint8_t)(((bits >> k) & 1u) ^ (negate ? 1u : 0u));
+      }
     }
   }
 }
@@ -696,26 +831,18 @@ void str_like_segments(const int64_t* off, const uint8_t* chars, int64_t n, cons
   if (nseg > kSegMax) throw std::runtime_error("str_like_segments: too many segments");
   const bool dword_filter = !debug_flag("like_nodword");
   if (dword_filter && nseg >= 1 && nseg <= 2 && min_seg >= 7) {
-    const dim3 g(grid_for(n, kBlock, 256 * 8 * 4)), b(kBlock);
-    constexpr int u = 1;   // (2 and 4 rows per lane measured no faster: profiles/r5_ab_like_*.txt)
-#define IGLOO_LIKE_DWORD(S, U)                                                                                  \
-  hipLaunchKernelGGL((like_dword_kernel<S, kLikeDwordTile, U>), g, b, 0, stream, off, chars, n, seg, seg_off, nseg, \
-                     anchor_start, anchor_end, negate, out, nbytes)
-    if (nseg == 1) {
-      if (u >= 4) IGLOO_LIKE_DWORD(1, 4);
-      else if (u == 2) IGLOO_LIKE_DWORD(1, 2);
-      else IGLOO_LIKE_DWORD(1, 1);
-    } else {
-      if (u >= 4) IGLOO_LIKE_DWORD(2, 4);
-      else if (u == 2) IGLOO_LIKE_DWORD(2, 2);
-      else IGLOO_LIKE_DWORD(2, 1);
-    }
-#undef IGLOO_LIKE_DWORD
+    // 8 workgroups per CU, half of them resident at a time, each walking
+    // several tiles (like_few_wgs: two workgroups, so that a test-sized column
+    // gives each many tiles)
+    const int64_t max_wgs = debug_flag("like_few_wgs") ? 2 : 256 * 8;
+    hipLaunchKernelGGL((like_stream_kernel<kLikeStreamChunks>), dim3(grid_for(n, kLikeStreamRows, max_wgs)), dim3(kBlock),
+                       0, stream, off, chars, n, seg, seg_off, nseg, anchor_start, anchor_end, negate, out, nbytes);
     check_launch("str_like_segments", stream);
     return;
   }
-  // (a one-wave-per-workgroup variant with 4 / 8 KB tiles measured slower for
-  // Q13 at SF100, 14.6 vs 11.7 ms per query: profiles/r3_ab_like_wave.txt)
+  // like_seg_kernel. (a one-wave-per-workgroup variant with 4 / 8 KB tiles
+  // measured slower for Q13 at SF100, 14.6 vs 11.7 ms per query:
+  // profiles/r3_ab_like_wave.txt)
   // one or two segments (nearly every analytic LIKE): a bitmap sized for
   // them frees 4-6 KB of LDS per workgroup, one or two more resident
   // workgroups per CU (-9 % / -10 % for two / one segment,
