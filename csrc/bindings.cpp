@@ -682,6 +682,44 @@ PYBIND11_MODULE(_native, m) {
                         P<const uint8_t>(qvalid), nq, P<uint8_t>(hit), P<int32_t>(pos), P<const void>(fence), nf,
                         S(s));
   });
+  // two-level rank index (ranges.hip): build steps, then the lookups through it
+  m.def("rank_index_bits", [](uintptr_t big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, uintptr_t entries,
+                              uintptr_t s) {
+    if (nb <= 0 || kmax < kmin || !big || !entries || (entries & 15))
+      throw std::runtime_error("rank_index_bits: bad arguments");
+    kern::rank_index_bits(P<const void>(big), key64, nb, kmin, kmax, P<void>(entries), S(s));
+  });
+  m.def("rank_index_counts", [](uintptr_t entries, int64_t nwords, uintptr_t counts, uintptr_t s) {
+    if (nwords <= 0 || !entries || !counts) throw std::runtime_error("rank_index_counts: bad arguments");
+    kern::rank_index_counts(P<const void>(entries), nwords, P<int32_t>(counts), S(s));
+  });
+  m.def("rank_index_finish", [](uintptr_t entries, int64_t nwords, uintptr_t offsets, uintptr_t s) {
+    if (nwords <= 0 || !entries || !offsets) throw std::runtime_error("rank_index_finish: bad arguments");
+    kern::rank_index_finish(P<void>(entries), nwords, P<const int64_t>(offsets), S(s));
+  });
+  m.def("rank_index_starts", [](uintptr_t big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, uintptr_t entries,
+                                uintptr_t starts, bool starts64, int64_t nd, uintptr_t s) {
+    if (nb <= 0 || kmax < kmin || nd < 0 || !big || !entries || !starts)
+      throw std::runtime_error("rank_index_starts: bad arguments");
+    kern::rank_index_starts(P<const void>(big), key64, nb, kmin, kmax, P<const void>(entries), P<void>(starts),
+                            starts64, nd, S(s));
+  });
+  m.def("rank_ranges", [](uintptr_t entries, uintptr_t starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                          uintptr_t q, bool key64, uintptr_t qvalid, int64_t nq, uintptr_t lo, uintptr_t cnt,
+                          uintptr_t s) {
+    if (kmax < kmin || (entries & 15) || (nq > 0 && (!q || !lo || !cnt)))
+      throw std::runtime_error("rank_ranges: bad arguments");
+    kern::rank_ranges(P<const void>(entries), P<const void>(starts), starts64, nd, kmin, kmax, P<const void>(q), key64,
+                      P<const uint8_t>(qvalid), nq, P<int64_t>(lo), P<int64_t>(cnt), S(s));
+  });
+  m.def("rank_unique", [](uintptr_t entries, uintptr_t starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                          uintptr_t q, bool key64, uintptr_t qvalid, int64_t nq, uintptr_t hit, uintptr_t pos,
+                          uintptr_t s) {
+    if (kmax < kmin || (entries & 15) || (nq > 0 && (!q || !hit || !pos)))
+      throw std::runtime_error("rank_unique: bad arguments");
+    kern::rank_unique(P<const void>(entries), P<const void>(starts), starts64, nd, kmin, kmax, P<const void>(q), key64,
+                      P<const uint8_t>(qvalid), nq, P<uint8_t>(hit), P<int32_t>(pos), S(s));
+  });
   m.def("sorted_exists", [](uintptr_t big2, uintptr_t small2, bool key64, uintptr_t lo, uintptr_t cnt, int64_t ns,
                             int op, uintptr_t mask, uintptr_t hit, uintptr_t s) {
     // op 6 (any row of the range set in mask) reads neither value column

@@ -595,6 +595,25 @@ void dense_index_build(const void* big, bool key64, int64_t nb, int64_t kmin, in
                        int32_t* long_gap, hipStream_t stream);
 void dense_ranges(const void* first, bool first64, int64_t kmin, int64_t kmax, const void* q, bool key64,
                   const uint8_t* qvalid, int64_t nq, int64_t* lo, int64_t* cnt, hipStream_t stream);
+// two-level rank index of a sorted key column (ranges.hip, dense-index section): entries holds one
+// 16-byte {presence word, distinct keys before it} per 64 key values of [kmin, kmax], starts[r] the first
+// row of the r-th distinct key (nd + 1 entries, starts[nd] = the first row past kmax).
+// Build: rank_index_bits into zeroed entries, rank_index_counts, an exclusive scan of the counts,
+// rank_index_finish, then (non-unique columns) rank_index_starts.
+void rank_index_bits(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, void* entries,
+                     hipStream_t stream);
+void rank_index_counts(const void* entries, int64_t nwords, int32_t* counts, hipStream_t stream);
+void rank_index_finish(void* entries, int64_t nwords, const int64_t* offsets, hipStream_t stream);
+void rank_index_starts(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, const void* entries,
+                       void* starts, bool starts64, int64_t nd, hipStream_t stream);
+// lookups through it, outputs as dense_ranges / unique_lookup. entries == null: keys contiguous from
+// kmin (rank = key - kmin); starts == null: keys distinct (row = rank)
+void rank_ranges(const void* entries, const void* starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                 const void* q, bool key64, const uint8_t* qvalid, int64_t nq, int64_t* lo, int64_t* cnt,
+                 hipStream_t stream);
+void rank_unique(const void* entries, const void* starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                 const void* q, bool key64, const uint8_t* qvalid, int64_t nq, uint8_t* hit, int32_t* pos,
+                 hipStream_t stream);
 // probe keys into DISTINCT sorted keys (nb < 2^31): hit[i] 0/1 and pos[i] (int32 row, 0 on a miss);
 // first != null: through the dense lower-bound table, else a (fenced) binary search of big
 void unique_lookup(const void* big, bool key64, int64_t nb, const void* first, bool first64, int64_t kmin,

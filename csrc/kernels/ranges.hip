@@ -289,6 +289,25 @@ void sorted_masked(const uint8_t* mask, const int64_t* lo, const int64_t* cnt, i
 // whose probes miss the cache when the queries arrive in random key order
 // (Q9 probes partsupp in lineitem order: 11 ms searching vs ~1 ms indexed).
 // Row i fills the entries between the previous row's key and its own.
+//
+// That flat table spends 4 bytes per key VALUE, and a lookup fetches a 128-byte
+// line of it to learn one entry (orders.o_orderkey at SF100: 2.4 GB for 150M
+// rows). Large resident columns (ops/hashing.py dense_index picks the form)
+// get a two-level index instead:
+//   rank level: one 16-byte entry per 64 key values, {64-bit presence word,
+//     number of distinct keys in all earlier entries}: 0.25 B per key value,
+//     one load per lookup. present = bit (k - kmin) & 63 of the word;
+//     r = rank + popcount(bits below it) = distinct keys < k.
+//   starts level (columns with repeated keys): starts[r] = first row of the
+//     r-th distinct key, starts[nd] = first row past kmax, so
+//     lo = starts[r] (the lower bound for absent keys too) and
+//     cnt = present ? starts[r + 1] - starts[r] : 0.
+// The four forms: distinct contiguous keys need no table (row = k - kmin);
+// distinct keys with holes the rank level alone (row = r); repeated keys
+// with no holes the flat table (it IS the starts level under an identity
+// rank); repeated keys with holes both levels. The build sets presence bits
+// from the run starts (rows whose key differs from the previous row's), scans
+// their popcounts and scatters the run starts: no flat table, no gap filling.
 namespace igloo {
 namespace kern {
 namespace {
@@ -352,6 +371,180 @@ __global__ __launch_bounds__(kBlock) void dense_ranges_kernel(const I* __restric
   }
 }
 
+// ---- the two-level form ----
+struct alignas(16) RankEntry {
+  uint64_t bits;   // key kmin + 64 * w + b is in the column <=> bit b
+  uint32_t rank;   // distinct keys in entries [0, w)
+  uint32_t pad;
+};
+typedef uint32_t RankWords __attribute__((ext_vector_type(4)));
+
+constexpr int kRankChunk = 16;  // build: consecutive rows per lane, their bits merged before the atomic
+constexpr int kRankRows = 4;    // lookup: probe rows in flight per lane (two dependent loads each)
+
+// presence bits from the run starts. A lane walks kRankChunk consecutive rows
+// and ORs the bits that share a word in a register: sorted keys change word
+// rarely, so it issues one or two atomics, not one per row. Keys outside
+// [kmin, kmax] (a recorded range narrower than the data) set nothing.
+template <typename K>
+__global__ __launch_bounds__(kBlock) void rank_bits_kernel(const K* __restrict__ big, int64_t nb, int64_t kmin,
+                                                          int64_t kmax, RankEntry* __restrict__ e) {
+  const int64_t nchunk = (nb + kRankChunk - 1) / kRankChunk;
+  for (int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; c < nchunk; c += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i0 = c * kRankChunk, i1 = i0 + kRankChunk < nb ? i0 + kRankChunk : nb;
+    int64_t prev = i0 > 0 ? (int64_t)big[i0 - 1] : 0;
+    int64_t w = -1;
+    uint64_t acc = 0;
+    for (int64_t i = i0; i < i1; ++i) {
+      const int64_t cur = (int64_t)big[i];
+      if ((i == 0 || cur != prev) && cur >= kmin && cur <= kmax) {
+        const int64_t j = cur - kmin;
+        if ((j >> 6) != w) {
+          if (acc) atomicOr((unsigned long long*)&e[w].bits, (unsigned long long)acc);
+          w = j >> 6;
+          acc = 0;
+        }
+        acc |= uint64_t{1} << (j & 63);
+      }
+      prev = cur;
+    }
+    if (acc) atomicOr((unsigned long long*)&e[w].bits, (unsigned long long)acc);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void rank_counts_kernel(const RankEntry* __restrict__ e, int64_t nw,
+                                                            int32_t* __restrict__ counts) {
+  for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x)
+    counts[w] = __popcll(e[w].bits);
+}
+
+__global__ __launch_bounds__(kBlock) void rank_finish_kernel(RankEntry* __restrict__ e, int64_t nw,
+                                                            const int64_t* __restrict__ off) {
+  for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nw; w += (int64_t)gridDim.x * blockDim.x)
+    e[w].rank = (uint32_t)off[w];
+}
+
+// (present, r = distinct keys < kmin + j) for j in [0, span); RANKED false:
+// every key value present, r = j
+template <bool RANKED>
+__device__ inline void rank_locate(const RankEntry* __restrict__ e, int64_t j, bool& present, int64_t& r) {
+  if (!RANKED) {
+    present = true;
+    r = j;
+    return;
+  }
+  const RankWords v = *reinterpret_cast<const RankWords*>(e + (j >> 6));   // one 16-byte load: word and rank
+  const uint64_t bits = (uint64_t)v.x | ((uint64_t)v.y << 32);
+  const int b = (int)(j & 63);
+  present = (bits >> b) & 1;
+  r = (int64_t)v.z + __popcll(bits & ((uint64_t{1} << b) - 1));
+}
+
+// run starts scattered to their rank; the one row (or nb) where the keys pass
+// kmax closes the last run. r < nd holds by construction (the bits came from
+// the same rows); the test keeps a changed column from writing past starts.
+template <typename K, typename S>
+__global__ __launch_bounds__(kBlock) void rank_starts_kernel(const K* __restrict__ big, int64_t nb, int64_t kmin,
+                                                            int64_t kmax, const RankEntry* __restrict__ e,
+                                                            S* __restrict__ starts, int64_t nd) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= nb; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t prev = i > 0 ? (int64_t)big[i - 1] : 0;
+    const int64_t cur = i < nb ? (int64_t)big[i] : 0;
+    if (i < nb && (i == 0 || cur != prev) && cur >= kmin && cur <= kmax) {
+      bool present;
+      int64_t r;
+      rank_locate<true>(e, cur - kmin, present, r);
+      if (r < nd) starts[r] = (S)i;
+    }
+    if ((i == nb || cur > kmax) && (i == 0 || prev <= kmax)) starts[nd] = (S)i;
+  }
+}
+
+// The lookups keep kRankRows probe rows per lane in flight: all keys are
+// loaded, then all entries, then all starts. Every load is unconditional (a
+// row past the end re-reads row nq - 1, a key outside [kmin, kmax] or a NULL
+// reads entry 0, starts[r + 1] is clamped to starts[nd]) so the compiler
+// batches them instead of branching around and waiting for each.
+template <typename K, bool VALID>
+__device__ inline void rank_probe_keys(const K* __restrict__ q, const uint8_t* __restrict__ qvalid, int64_t nq,
+                                       int64_t t0, int64_t kmin, int64_t kmax, bool (&in)[kRankRows],
+                                       bool (&ok)[kRankRows], int64_t (&j)[kRankRows]) {
+#pragma unroll
+  for (int u = 0; u < kRankRows; ++u) {
+    const int64_t i = t0 + (int64_t)u * kBlock + threadIdx.x;
+    in[u] = i < nq;
+    const int64_t ii = in[u] ? i : nq - 1;
+    const int64_t k = (int64_t)q[ii];
+    bool v = in[u] && k >= kmin && k <= kmax;
+    if (VALID) v = v && qvalid[ii] != 0;
+    ok[u] = v;
+    j[u] = v ? k - kmin : 0;
+  }
+}
+
+template <typename K, typename S, bool RANKED, bool STARTS, bool VALID>
+__global__ __launch_bounds__(kBlock) void rank_ranges_kernel(const RankEntry* __restrict__ e,
+                                                            const S* __restrict__ starts, int64_t nd, int64_t kmin,
+                                                            int64_t kmax, const K* __restrict__ q,
+                                                            const uint8_t* __restrict__ qvalid, int64_t nq,
+                                                            int64_t* __restrict__ lo_out,
+                                                            int64_t* __restrict__ cnt_out) {
+  constexpr int64_t kTile = (int64_t)kBlock * kRankRows;
+  for (int64_t t0 = blockIdx.x * kTile; t0 < nq; t0 += (int64_t)gridDim.x * kTile) {
+    bool in[kRankRows], ok[kRankRows], present[kRankRows];
+    int64_t j[kRankRows], r[kRankRows], lo[kRankRows], c[kRankRows];
+    rank_probe_keys<K, VALID>(q, qvalid, nq, t0, kmin, kmax, in, ok, j);
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) rank_locate<RANKED>(e, j[u], present[u], r[u]);
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) {
+      if (STARTS) {
+        const int64_t r1 = r[u] < nd ? r[u] + 1 : nd;
+        lo[u] = (int64_t)starts[r[u]];
+        c[u] = (int64_t)starts[r1] - lo[u];
+      } else {
+        lo[u] = r[u];
+        c[u] = 1;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) {
+      const int64_t i = t0 + (int64_t)u * kBlock + threadIdx.x;
+      if (in[u]) {
+        lo_out[i] = ok[u] ? lo[u] : 0;
+        cnt_out[i] = ok[u] && present[u] ? c[u] : 0;
+      }
+    }
+  }
+}
+
+template <typename K, typename S, bool RANKED, bool STARTS, bool VALID>
+__global__ __launch_bounds__(kBlock) void rank_unique_kernel(const RankEntry* __restrict__ e,
+                                                            const S* __restrict__ starts, int64_t nd, int64_t kmin,
+                                                            int64_t kmax, const K* __restrict__ q,
+                                                            const uint8_t* __restrict__ qvalid, int64_t nq,
+                                                            uint8_t* __restrict__ hit, int32_t* __restrict__ pos) {
+  constexpr int64_t kTile = (int64_t)kBlock * kRankRows;
+  for (int64_t t0 = blockIdx.x * kTile; t0 < nq; t0 += (int64_t)gridDim.x * kTile) {
+    bool in[kRankRows], ok[kRankRows], present[kRankRows];
+    int64_t j[kRankRows], r[kRankRows], row[kRankRows];
+    rank_probe_keys<K, VALID>(q, qvalid, nq, t0, kmin, kmax, in, ok, j);
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) rank_locate<RANKED>(e, j[u], present[u], r[u]);
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) row[u] = STARTS ? (int64_t)starts[r[u]] : r[u];
+#pragma unroll
+    for (int u = 0; u < kRankRows; ++u) {
+      const int64_t i = t0 + (int64_t)u * kBlock + threadIdx.x;
+      if (in[u]) {
+        const bool h = ok[u] && present[u];
+        hit[i] = h ? 1 : 0;
+        pos[i] = h ? (int32_t)row[u] : 0;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 void dense_index_build(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, void* first, bool first64,
@@ -382,6 +575,76 @@ void dense_ranges(const void* first, bool first64, int64_t kmin, int64_t kmax, c
     using I = type_of<decltype(i)>;
     launch("dense_ranges", dense_ranges_kernel<K, I>, g, b, 0, stream, as<I>(first), kmin, kmax, as<K>(q), qvalid, nq,
            lo, cnt);
+  });
+}
+
+void rank_index_bits(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, void* entries,
+                     hipStream_t stream) {
+  if (nb <= 0) return;
+  const dim3 g(grid_for((nb + kRankChunk - 1) / kRankChunk, kBlock, 1 << 16)), b(kBlock);
+  dispatch(wide{key64}, [&](auto k) {
+    using K = type_of<decltype(k)>;
+    launch("rank_index_bits", rank_bits_kernel<K>, g, b, 0, stream, as<K>(big), nb, kmin, kmax,
+           as<RankEntry>(entries));
+  });
+}
+
+void rank_index_counts(const void* entries, int64_t nwords, int32_t* counts, hipStream_t stream) {
+  if (nwords <= 0) return;
+  launch("rank_index_counts", rank_counts_kernel, dim3(grid_for(nwords, kBlock, 1 << 16)), dim3(kBlock), 0, stream,
+         as<RankEntry>(entries), nwords, counts);
+}
+
+void rank_index_finish(void* entries, int64_t nwords, const int64_t* offsets, hipStream_t stream) {
+  if (nwords <= 0) return;
+  launch("rank_index_finish", rank_finish_kernel, dim3(grid_for(nwords, kBlock, 1 << 16)), dim3(kBlock), 0, stream,
+         as<RankEntry>(entries), nwords, offsets);
+}
+
+void rank_index_starts(const void* big, bool key64, int64_t nb, int64_t kmin, int64_t kmax, const void* entries,
+                       void* starts, bool starts64, int64_t nd, hipStream_t stream) {
+  const dim3 g(grid_for(nb + 1, kBlock, 1 << 16)), b(kBlock);
+  dispatch(wide{key64}, wide{starts64}, [&](auto k, auto s) {
+    using K = type_of<decltype(k)>;
+    using S = type_of<decltype(s)>;
+    launch("rank_index_starts", rank_starts_kernel<K, S>, g, b, 0, stream, as<K>(big), nb, kmin, kmax,
+           as<RankEntry>(entries), as<S>(starts), nd);
+  });
+}
+
+void rank_ranges(const void* entries, const void* starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                 const void* q, bool key64, const uint8_t* qvalid, int64_t nq, int64_t* lo, int64_t* cnt,
+                 hipStream_t stream) {
+  if (nq <= 0) return;
+  const dim3 g(grid_for(nq, kBlock * kRankRows, 1 << 16)), b(kBlock);
+  pick(qvalid != nullptr, [&](auto v) {
+    dispatch(wide{key64}, wide{starts64}, entries != nullptr, starts != nullptr,
+             [&](auto k, auto s, auto rk, auto st) {
+               using K = type_of<decltype(k)>;
+               using S = type_of<decltype(s)>;
+               constexpr bool kRanked = decltype(rk)::value, kStarts = decltype(st)::value;
+               constexpr bool kValid = decltype(v)::value;
+               launch("rank_ranges", rank_ranges_kernel<K, S, kRanked, kStarts, kValid>, g, b, 0, stream,
+                      as<RankEntry>(entries), as<S>(starts), nd, kmin, kmax, as<K>(q), qvalid, nq, lo, cnt);
+             });
+  });
+}
+
+void rank_unique(const void* entries, const void* starts, bool starts64, int64_t nd, int64_t kmin, int64_t kmax,
+                 const void* q, bool key64, const uint8_t* qvalid, int64_t nq, uint8_t* hit, int32_t* pos,
+                 hipStream_t stream) {
+  if (nq <= 0) return;
+  const dim3 g(grid_for(nq, kBlock * kRankRows, 1 << 16)), b(kBlock);
+  pick(qvalid != nullptr, [&](auto v) {
+    dispatch(wide{key64}, wide{starts64}, entries != nullptr, starts != nullptr,
+             [&](auto k, auto s, auto rk, auto st) {
+               using K = type_of<decltype(k)>;
+               using S = type_of<decltype(s)>;
+               constexpr bool kRanked = decltype(rk)::value, kStarts = decltype(st)::value;
+               constexpr bool kValid = decltype(v)::value;
+               launch("rank_unique", rank_unique_kernel<K, S, kRanked, kStarts, kValid>, g, b, 0, stream,
+                      as<RankEntry>(entries), as<S>(starts), nd, kmin, kmax, as<K>(q), qvalid, nq, hit, pos);
+             });
   });
 }
 

@@ -488,10 +488,20 @@ DENSE_INDEX_MAX_SPAN_RATIO = 4      # table entries per indexed row (orders: 1 o
 
 
 def dense_index(big: torch.Tensor, build: bool = True, queries: Optional[int] = None):
-    """Lower-bound table of a sorted key column (csrc/kernels/ranges.hip):
-    ``(kmin, kmax, first)`` with first[k - kmin] = first row whose key >= k,
-    or None when the key span is too sparse. Remembered on the tensor object
-    (resident table columns build it once)."""
+    """Key-value index of a sorted key column (csrc/kernels/ranges.hip), or
+    None when the key span is too sparse. Remembered on the tensor object
+    (resident table columns build it once). Its form (``dense_form``):
+
+    * ``(kmin, kmax, first)``: the flat lower-bound table, first[k - kmin] =
+      first row whose key >= k. Every index of fewer than
+      ``RANK_INDEX_MIN_ENTRIES`` entries, every intermediate's, and large
+      resident columns whose keys repeat and leave no hole.
+    * ``(kmin, kmax, starts, entries, ndistinct)``: a large resident column's
+      two-level index (``rank_index_form``). ``entries`` holds per 64 key
+      values a presence word and the distinct keys before it, ``starts`` the
+      first row of each distinct key (``ndistinct + 1`` rows). Distinct keys
+      need no ``starts`` (None: row = rank); distinct keys without holes no
+      ``entries`` either (None: row = k - kmin)."""
     hit = tags.DENSE.get(big)
     # (the sorted keys of a resident column's secondary index live as long as
     # the column: their table is built once too -- Q9's 1.1M green parts
@@ -531,6 +541,91 @@ def _dense_limit(nb: int, queries: Optional[int], resident: bool = False) -> int
     return DENSE_INDEX_MAX_SPAN_RATIO * min(nb, queries if queries is not None else nb) + 4096
 
 
+#: index entries (key span + 1) from which a resident column's index takes the
+#: two-level forms. Below it the flat table stays: 2^20 int32 entries are
+#: 4 MiB, one XCD's L2, so its lookups are served on chip and a smaller
+#: structure saves no HBM traffic, while the rank level adds a popcount and
+#: (for repeated keys) a dependent load. SF100's supplier keys (1M) stay flat;
+#: customer (15M), part (20M), orders and lineitem (600M key values) do not.
+RANK_INDEX_MIN_ENTRIES = 1 << 20
+#: False: columns with repeated keys and holes keep the flat table
+RANK_INDEX_STARTS = not _sw.debug("rank_flat_starts")
+
+FLAT, IDENTITY, RANK, RANK_STARTS = "flat", "identity", "rank", "rank+starts"
+
+
+def rank_index_form(nb: int, ndistinct: int, span: int) -> str:
+    """Form of the index over ``nb`` sorted rows holding ``ndistinct``
+    different keys in a span of ``span`` key values: distinct keys need no
+    starts level, keys without holes no rank level (the flat table is the
+    starts level under an identity rank)."""
+    if ndistinct == nb:
+        return IDENTITY if nb == span else RANK
+    return FLAT if ndistinct == span or not RANK_INDEX_STARTS else RANK_STARTS
+
+
+def rank_index_nbytes(form: str, nb: int, ndistinct: int, span: int) -> int:
+    """Device bytes of an index of that form (what utils/memory.py charges)."""
+    width = 8 if nb >= INT32_MAX else 4
+    if form == FLAT:
+        return (span + 1) * width
+    entries = 16 * ((span + 63) // 64) if form in (RANK, RANK_STARTS) else 0
+    return entries + ((ndistinct + 1) * width if form == RANK_STARTS else 0)
+
+
+def dense_form(idx) -> str:
+    """Which form a ``dense_index`` result has."""
+    if len(idx) == 3:
+        return FLAT
+    _, _, starts, entries, _ = idx
+    return IDENTITY if entries is None else RANK if starts is None else RANK_STARTS
+
+
+def _rank_index_build(big: torch.Tensor, kmin: int, kmax: int):
+    """The two-level index of a resident column (ranges.hip): presence bits
+    from the run starts, an exclusive scan of their popcounts, and the run
+    starts scattered to their ranks. None when the form is the flat table."""
+    nb, span = big.numel(), kmax - kmin + 1
+    nw = (span + 63) // 64
+    N = launch("rank_index_build")
+    st, key64, dev = stream(big), big.dtype == torch.int64, big.device
+    entries = torch.zeros(2 * nw, dtype=torch.int64, device=dev)     # 16 bytes each: (word, rank)
+    N.rank_index_bits(ptr(big), key64, nb, kmin, kmax, ptr(entries), st)
+    counts = torch.empty(nw, dtype=torch.int32, device=dev)
+    N.rank_index_counts(ptr(entries), nw, ptr(counts), st)
+    off, nd = exclusive_scan(counts)
+    form = rank_index_form(nb, nd, span)
+    if form == FLAT:
+        return None
+    if form == IDENTITY:
+        return (kmin, kmax, None, None, nd)
+    N.rank_index_finish(ptr(entries), nw, ptr(off), st)
+    if form == RANK:
+        return (kmin, kmax, None, entries, nd)
+    starts = torch.empty(nd + 1, dtype=torch.int64 if nb >= INT32_MAX else torch.int32, device=dev)
+    N.rank_index_starts(ptr(big), key64, nb, kmin, kmax, ptr(entries), ptr(starts), starts.dtype == torch.int64, nd, st)
+    return (kmin, kmax, starts, entries, nd)
+
+
+def _flat_index_build(big: torch.Tensor, kmin: int, kmax: int):
+    nb, span = big.numel(), kmax - kmin + 1
+    it = torch.int64 if nb >= INT32_MAX else torch.int32
+    first = torch.empty(span + 1, dtype=it, device=big.device)
+    gap = torch.zeros(1, dtype=torch.int32, device=big.device)
+    N = launch("dense_index_build")
+    st = stream(big)
+    N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
+                        it == torch.int64, ptr(gap), st)
+    if to_host_int(gap):
+        # long key gaps: rebuild over a -1 fill, then search the entries left at -1
+        first.fill_(-1)
+        N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
+                            it == torch.int64, ptr(gap), st)
+        N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
+                            it == torch.int64, 0, st)
+    return (kmin, kmax, first)
+
+
 def _dense_index_build(big: torch.Tensor, queries: Optional[int], resident: bool = False):
     nb = big.numel()
     idx = False
@@ -542,21 +637,14 @@ def _dense_index_build(big: torch.Tensor, queries: Optional[int], resident: bool
         kmin, kmax = rng
         span = kmax - kmin + 1
         if span <= _dense_limit(nb, queries, resident):
-            it = torch.int64 if nb >= INT32_MAX else torch.int32
-            first = torch.empty(span + 1, dtype=it, device=big.device)
-            gap = torch.zeros(1, dtype=torch.int32, device=big.device)
-            N = launch("dense_index_build")
-            st = stream(big)
-            N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
-                                it == torch.int64, ptr(gap), st)
-            if to_host_int(gap):
-                # long key gaps: rebuild over a -1 fill, then search the entries left at -1
-                first.fill_(-1)
-                N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
-                                    it == torch.int64, ptr(gap), st)
-                N.dense_index_build(ptr(big), big.dtype == torch.int64, nb, kmin, kmax, ptr(first),
-                                    it == torch.int64, 0, st)
-            idx = (kmin, kmax, first)
+            idx = None
+            # (resident columns only: an intermediate's index is rebuilt every
+            # execution, where the scan's readback would cost more than it saves;
+            # ranks are 32-bit)
+            if resident and span + 1 > RANK_INDEX_MIN_ENTRIES and span < 2**32:
+                idx = _rank_index_build(big, kmin, kmax)
+            if idx is None:
+                idx = _flat_index_build(big, kmin, kmax)
     tags.DENSE.set(big, idx)
     return idx or None
 
@@ -577,6 +665,13 @@ def sorted_ranges(big: torch.Tensor, q: torch.Tensor, qvalid: Optional[torch.Ten
     lo = torch.empty(nq, dtype=torch.int64, device=big.device)
     cnt = torch.empty(nq, dtype=torch.int64, device=big.device)
     idx = dense_index(big, build=nq >= DENSE_INDEX_MIN_QUERIES, queries=nq) if DENSE_INDEX else None
+    if idx and len(idx) > 3:
+        kmin, kmax, starts, entries, nd = idx
+        launch("rank_ranges").rank_ranges(ptr(entries), ptr(starts), starts is not None and starts.dtype == torch.int64,
+                                          nd, kmin, kmax, ptr(q), q.dtype == torch.int64,
+                                          ptr(qvalid.contiguous() if qvalid is not None else None), nq, ptr(lo),
+                                          ptr(cnt), stream(big))
+        return lo, cnt
     if idx:
         kmin, kmax, first = idx
         launch("dense_ranges").dense_ranges(ptr(first), first.dtype == torch.int64, kmin, kmax, ptr(q),
@@ -616,6 +711,12 @@ def unique_lookup(big: torch.Tensor, q: torch.Tensor, qvalid: Optional[torch.Ten
     pos = torch.empty(nq, dtype=torch.int32, device=big.device)
     qv = ptr(qvalid.contiguous()) if qvalid is not None else 0
     idx = dense_index(big, build=nq >= DENSE_INDEX_MIN_QUERIES, queries=nq) if DENSE_INDEX else None
+    if idx and len(idx) > 3:
+        kmin, kmax, starts, entries, nd = idx
+        launch("rank_unique").rank_unique(ptr(entries), ptr(starts), starts is not None and starts.dtype == torch.int64,
+                                          nd, kmin, kmax, ptr(q), q.dtype == torch.int64, qv, nq, ptr(hit), ptr(pos),
+                                          stream(big))
+        return hit, pos
     N = launch("unique_lookup")
     if idx:
         kmin, kmax, first = idx

@@ -38,6 +38,9 @@ list of tokens (``token`` or ``token=value``), read by Python and C++ alike
                                 selection counts the mask again, ops/select.py)
 ``pack_bits_scalar``            composite-key packing one row per lane instead of four
                                 with 16-byte loads (util.hip pack_bits)
+``rank_flat_starts``            sorted resident key columns with repeated keys and holes
+                                keep the flat lower-bound table instead of the rank +
+                                starts index (ops/hashing.py RANK_INDEX_STARTS)
 ==============================  =====================================================
 
 Other variables (each read in one place):

@@ -54,7 +54,8 @@ ORIGIN = Tag("_igloo_origin", LINEAGE, "the resident column every value was gath
 # ---- derived: device buffers built once on a resident column and charged to it (utils/memory.py)
 NARROW = Tag("_igloo_narrow", DERIVED_KIND, "narrowest integer copy, or the column itself when none is narrower (exec/fused.py)")
 PERM = Tag("_igloo_perm", DERIVED_KIND, "(keys in sorted order, int32 row permutation) (ops/hashing.py perm_index)")
-DENSE = Tag("_igloo_dense", DERIVED_KIND, "None: not tried; False: too sparse; (kmin, kmax, first) lower-bound table (dense_index)")
+DENSE = Tag("_igloo_dense", DERIVED_KIND, "None: not tried; False: too sparse; (kmin, kmax, first) lower-bound table, or a large resident column's "
+            "(kmin, kmax, starts | None, entries | None, ndistinct) rank index (dense_index)")
 HLL = Tag("_igloo_hll", DERIVED_KIND, "HyperLogLog registers, uint8 [4096] (ops/hashing.py hll_sketch)")
 FENCE = Tag("_igloo_fence", DERIVED_KIND, "every 256th key of a sorted column (ops/hashing.py search_fence)")
 PACKED = Tag("_igloo_packed", DERIVED_KIND, "row-packed copies of column sets, on a set's first column (ops/packed_gather.py)")
