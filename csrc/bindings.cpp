@@ -768,6 +768,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("str_pair_int", raw<&kern::str_pair_int>);
   m.def("str_levenshtein", raw<&kern::str_levenshtein>);
   m.def("str_levenshtein_long", raw<&kern::str_levenshtein_long>);
+  m.def("str_row_cmp", raw<&kern::str_row_cmp>);
   m.def("win_scan_tiles", &kern::win_scan_tiles);
   m.def("win_seg_scan", raw<&kern::win_seg_scan>);
   m.def("win_bounds", raw<&kern::win_bounds>);

@@ -771,6 +771,11 @@ void str_levenshtein(const int64_t* oa, const uint8_t* ca, bool ba, const int64_
 void str_levenshtein_long(const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb,
                           int64_t n, int32_t* out, int32_t* scratch, int64_t lanes, int64_t cells, hipStream_t s);
 
+// ---- strrow.hip (byte-wise three-way compare of two string operands per row: -1 / 0 / 1, a shorter
+// prefix first; either side may be a one-row column broadcast to every row)
+void str_row_cmp(const int64_t* oa, const uint8_t* ca, bool ba, const int64_t* ob, const uint8_t* cb, bool bb, int64_t n,
+                 int32_t* out, hipStream_t s);
+
 // ---- binary.hip (BINARY functions: hex / base64 encode and decode, UTF-8 validation) ----
 // err (int64[2], set to {n, 0} by the caller): [0] the smallest invalid row by atomicMin, [1] (hex) set
 // when a NULL row holds bytes. valid: one byte per row or null. Offsets need not start at 0.

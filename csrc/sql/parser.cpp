@@ -886,7 +886,7 @@ class Parser {
         auto n = make("like");
         if (next().text == "ILIKE") n->flags["ilike"] = "1";
         if (neg) n->flags["neg"] = "1";
-        n->kids = {l, additive()};
+        n->kids = {l, concat()};  // x LIKE prefix || '%': the pattern may be a concatenation
         if (acceptKw("ESCAPE")) n->attrs["escape"] = primary();
         l = n;
       } else if (!neg && acceptKw("IS")) {
@@ -1215,6 +1215,22 @@ class Parser {
             auto f = make("func", "strpos");
             f->kids = {hay, needle};
             return f;
+          }
+          if (lower(name) == "overlay") {  // OVERLAY(s PLACING t FROM a [FOR b]) -> overlay(s, t, a[, b])
+            auto save = p_;
+            ++p_;
+            NodeP s = expr();
+            // PLACING / FOR are matched as identifier text, not reserved: columns may carry the names
+            if (acceptWord("placing")) {
+              auto f = make("func", "overlay");
+              f->kids = {s, expr()};
+              expectKw("FROM");
+              f->kids.push_back(expr());
+              if (acceptWord("for")) f->kids.push_back(expr());
+              expectOp(")");
+              return f;
+            }
+            p_ = save;  // overlay(s, t, a[, b]): an ordinary call
           }
           return funcCall(name);
         }

@@ -565,6 +565,16 @@ class Evaluator:
             from ..ops import strfuncs as SF
             c = args[0]
             return Column(T.INT32, SF.apply_int(c, name, e.options), c.valid)
+        if name in _STRROW:
+            # arguments that vary per row (ops/strrow.py): a constant stays a constant
+            from ..ops import strrow as SR
+            strs, ints = _row_operands(name, [a.value if isinstance(a, Scalar) else a for a in args])
+            return SR.apply_rows(name[:-4], strs, ints, b.num_rows)
+        if name == "like_row":
+            from ..ops import strrow as SR
+            negated, esc = e.options
+            x, p = [(None if a.value is None else _text(a.value)) if isinstance(a, Scalar) else a for a in args]
+            return SR.like_rows(x, p, esc, negated, b.num_rows)
         if name in ("regexp_like", "regexp_count", "regexp_replace"):
             from ..ops import strfuncs as SF
             c = args[0]
@@ -811,8 +821,22 @@ class Evaluator:
             return Scalar(list(vals), e.dtype)
         if name == "struct":
             return Scalar(dict(zip(e.options, vals)), e.dtype)
+        if name in ("greatest", "least") and e.dtype.is_string:
+            # NULL arguments are skipped; byte-wise order, as the kernel compares
+            keys = [_text(v).encode("utf-8") for v in vals if v is not None]
+            return Scalar((max(keys) if name == "greatest" else min(keys)).decode("utf-8") if keys else None, e.dtype)
         if any(v is None for v in vals) and name not in _LIST_FAMILY + _MAP_FAMILY:   # own NULL rules
             return Scalar(None, e.dtype)
+        if name in _STRROW or name == "like_row":
+            from ..ops import strrow as SR
+            if name == "like_row":
+                negated, esc = e.options
+                return Scalar(SR.py_like(_text(vals[0]), _text(vals[1]), esc) != negated, T.BOOL)
+            strs, ints = _row_operands(name, vals)
+            try:
+                return Scalar(SR.py_row(name[:-4])(strs, ints), T.UTF8)
+            except ValueError as ex:
+                raise ExecutionError(str(ex)) from None
         if name == "upper":
             return Scalar(vals[0].upper(), T.UTF8)
         if name == "lower":
@@ -858,6 +882,9 @@ class Evaluator:
         n = b.num_rows
         dev = self.device(b)
         t = e.dtype
+        if t.is_string:
+            from ..ops import strrow as SR
+            return SR.extreme_rows([self._str_col(a, dev, t) for a in args], e.name == "greatest", n)
         out, valid = None, None
         for a in args:
             x, xv = _full_of(a, t, n, dev)
@@ -902,6 +929,23 @@ _STRFN = ("trim", "replace", "lpad", "rpad", "reverse", "repeat", "left", "right
           "split_part", "substr_index")
 # with two arguments: the per-row forms (one-argument strpos keeps its literal in the options)
 _STRPAIR = ("levenshtein", "strpos", "contains", "starts_with", "ends_with", "find_in_set")
+# per-row arguments (ops/strrow.py): the name, then which arguments are strings
+_STRROW = {"substr_row": (0,), "left_row": (0,), "right_row": (0,), "repeat_row": (0,), "split_part_row": (0, 1),
+           "lpad_row": (0, 2), "rpad_row": (0, 2), "replace_row": (0, 1, 2), "overlay_row": (0, 1), "chr_row": (),
+           "to_hex_row": ()}
+
+
+def _row_operands(name: str, vals: list):
+    """(string operands, integer operands) of a ``*_row`` call, in argument order; lpad / rpad
+    without a fill pad with a blank."""
+    at = _STRROW[name]
+    strs = [(_text(v) if v is not None and not isinstance(v, Column) else v) for i, v in enumerate(vals) if i in at]
+    ints = [(int(v) if v is not None and not isinstance(v, Column) else v) for i, v in enumerate(vals) if i not in at]
+    if name in ("lpad_row", "rpad_row") and len(strs) == 1:
+        strs.append(" ")
+    return strs, ints
+
+
 _MATH1 = ("sign", "trunc", "log2", "cbrt", "degrees", "radians", "sin", "cos", "tan", "asin", "acos", "atan", "sinh",
           "cosh", "tanh", "isnan", "iszero", "factorial")
 _US_DAY = 86_400_000_000

@@ -789,13 +789,13 @@ class Binder:
         if k == "like":
             x = self.bind_expr(node["c"][0], scope, allow_agg)
             p = self.bind_expr(node["c"][1], scope, allow_agg)
-            if not isinstance(p, Lit) or not isinstance(TPL.peek(p), str):
-                raise NotSupported("LIKE pattern must be a string literal")
             esc = "\\"
             if node.get("escape"):
                 esc = self.bind_expr(node["escape"], scope).value
-            if x.dtype.is_binary:
+            if x.dtype.is_binary or p.dtype.is_binary:
                 raise NotSupported("LIKE / ILIKE on a Binary operand (CAST it to VARCHAR, or encode() it)")
+            if not isinstance(p, Lit) or not isinstance(TPL.peek(p), str):
+                return self._like_row(x, p, esc, bool(node.get("neg")), bool(node.get("ilike")))
             e = Like(self._coerce(x, UTF8), TPL.peek(p), bool(node.get("neg")), bool(node.get("ilike")), esc)
             TPL.raw(e, "pattern", lambda a: a.value, p)      # (a template re-reads the pattern)
             return e
@@ -1216,7 +1216,9 @@ class Binder:
                 raise PlanError("substr takes 2 or 3 arguments")
             a = self._coerce(args[0], UTF8)
             if not all(isinstance(x, Lit) for x in args[1:]):
-                raise NotSupported("substr with non-literal positions")
+                # a position per row (ops/strrow.py); a literal sibling stays a Lit child
+                return Func("substr_row", [a] + [self._row_int("substr", i, x) for i, x in enumerate(args[1:], 1)],
+                            UTF8)
             start = int(args[1].value)
             ln = int(args[2].value) if len(args) == 3 else None
             if isinstance(a, Lit):
@@ -1705,6 +1707,27 @@ class Binder:
             return Func("hex_digest", [a], UTF8, (algo,))
         raise NotSupported(f"{name}() on a Binary argument (CAST it to VARCHAR, or encode() it)")
 
+    # ------------------------------------------------- per-row string arguments
+    def _row_int(self, name: str, i: int, a: Expr) -> Expr:
+        """Argument ``i`` of a per-row string function as INT64 (ops/strrow.py)."""
+        if not (a.dtype.is_integer or a.dtype.kind == "null"):
+            raise PlanError(f"{name}(): argument {i + 1} must be an integer, got {a.dtype}")
+        return self._coerce(a, INT64)
+
+    def _like_row(self, x: Expr, p: Expr, esc, negated: bool, ilike: bool) -> Expr:
+        """``x [NOT] LIKE p`` with a pattern read per row (ops/strrow.py like_rows). The escape
+        stays a constant; ILIKE is LIKE over lower() of both sides, so a letter cannot escape."""
+        from ..ops.strrow import escape_byte
+        if not (p.dtype.is_string or p.dtype.kind == "null"):
+            raise PlanError(f"LIKE pattern must be a string, got {p.dtype}")
+        escape_byte(esc, "ILIKE" if ilike else "LIKE")
+        x, p = self._coerce(x, UTF8), self._coerce(p, UTF8)
+        if ilike:
+            if esc and esc.isalpha():
+                raise NotSupported("ILIKE with a per-row pattern: the escape must not be a letter")
+            x, p = Func("lower", [x], UTF8), Func("lower", [p], UTF8)
+        return Func("like_row", [x, p], BOOL, (negated, esc or ""))
+
     # ------------------------------------------------------ function library
     def _func_library(self, name: str, args: List[Expr]) -> Expr:
         """DataFusion built-ins beyond the TPC-H set (strings, math, dates)."""
@@ -1737,6 +1760,15 @@ class Binder:
                 return Lit(SF.py_fn2(fname)(a.value, b.value), rt)
             return Func(fname, [a, b], rt)
 
+        def rowfn(fname, strs, lo, hi):
+            # an extra argument that is no literal (ops/strrow.py apply_rows): the arguments at
+            # ``strs`` bind as UTF8, the others as INT64; literal ones stay Lit children
+            if not lo <= len(args) <= hi:
+                raise PlanError(f"{name}() takes {lo}{'' if lo == hi else f' or {hi}'} arguments")
+            return Func(fname + "_row", [self._coerce(a, UTF8) if i in strs else self._row_int(name, i, a)
+                                         for i, a in enumerate(args)], UTF8)
+        all_lit = all(isinstance(a, Lit) for a in args[1:])
+
         def per_row(i):
             # the call has exactly two arguments and the i-th is no string literal
             return len(args) == 2 and not (isinstance(args[i], Lit) and isinstance(args[i].value, str))
@@ -1751,18 +1783,28 @@ class Binder:
             chars = lit_str(1, "trim characters") if len(args) > 1 else " "
             return strfn("trim", ({"ltrim": 1, "rtrim": 2}.get(name, 3), chars))
         if name == "replace":
+            if not all_lit:
+                return rowfn("replace", (0, 1, 2), 3, 3)
             return strfn("replace", (lit_str(1, "search string"), lit_str(2, "replacement")))
         if name in ("lpad", "rpad"):
+            if not all_lit:
+                return rowfn(name, (0, 2), 2, 3)
             return strfn(name, (lit_int(1, "length"), lit_str(2, "fill") if len(args) > 2 else " "))
         if name in ("reverse", "initcap"):
             return strfn(name, ())
         if name == "repeat":
+            if not all_lit:
+                return rowfn("repeat", (0,), 2, 2)
             return strfn("repeat", (lit_int(1, "count"),))
         if name in ("left", "right"):
+            if not all_lit:
+                return rowfn(name, (0,), 2, 2)
             return strfn(name, (lit_int(1, "length"),))
         if name == "translate":
             return strfn("translate", (lit_str(1, "from"), lit_str(2, "to")))
         if name == "split_part":
+            if not all_lit:
+                return rowfn("split_part", (0, 1), 3, 3)
             return strfn("split_part", (lit_str(1, "delimiter"), lit_int(2, "part")))
         if name in ("substr_index", "substring_index"):
             _nargs(name, args, 3)
@@ -1811,11 +1853,31 @@ class Binder:
         if name == "chr":
             if isinstance(args[0], Lit):
                 return Lit(None if args[0].value is None else chr(int(args[0].value)), UTF8)
-            raise NotSupported("chr() of a column")
+            _nargs(name, args, 1)
+            return Func("chr_row", [self._row_int(name, 0, args[0])], UTF8)
         if name == "to_hex":
             if isinstance(args[0], Lit):
                 return Lit(None if args[0].value is None else format(int(args[0].value) & (2**64 - 1), "x"), UTF8)
-            raise NotSupported("to_hex() of a column")
+            _nargs(name, args, 1)
+            return Func("to_hex_row", [self._row_int(name, 0, args[0])], UTF8)
+        if name == "overlay":
+            # overlay(s, t, a[, b]) = substr(s, 1, a - 1) || t || substr(s, a + b); literal calls fold
+            e = rowfn("overlay", (0, 1), 3, 4)
+            s, t, *pos = e.args
+            if all(isinstance(a, Lit) for a in e.args):
+                from ..ops.strrow import py_row
+                if any(a.value is None for a in e.args):
+                    return Lit(None, UTF8)
+                return Lit(py_row("overlay")([s.value, t.value], [int(a.value) for a in pos]), UTF8)
+            if all(isinstance(a, Lit) and a.value is not None for a in pos) and (len(pos) == 2 or (
+                    isinstance(t, Lit) and t.value is not None)):
+                # literal positions: the two literal substr calls and || that the definition names
+                a = int(pos[0].value)
+                b = int(pos[1].value) if len(pos) == 2 else len(t.value)
+                head = Func("substr", [s], UTF8, (1, a - 1)) if a > 1 else Lit("", UTF8)
+                tail = Func("substr", [s], UTF8, (max(a + b, 1), None))
+                return Func("concat", [Func("concat", [head, t], UTF8), tail], UTF8)
+            return e
         # ---- math
         if name == "mod":
             return self._arith("%", args[0], args[1])
@@ -1843,7 +1905,8 @@ class Binder:
                     t = a.dtype if t is None else (t if t == a.dtype else T.common_numeric(t, a.dtype))
             t = t or T.NULL
             if t.is_string:
-                raise NotSupported(f"{name}() over strings")
+                # byte-wise order, NULL arguments skipped (ops/strrow.py extreme_rows)
+                return Func(name, [self._coerce(a, UTF8) for a in args], UTF8)
             return Func(name, [self._coerce(a, t) for a in args], t)
         if name in ("gcd", "lcm"):
             return Func(name, [self._coerce(a, INT64) for a in args[:2]], INT64)

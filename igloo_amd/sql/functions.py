@@ -25,7 +25,7 @@ STRING: Dict[str, str] = {
     "octet_length": "octet_length(s)", "bit_length": "bit_length(s)", "starts_with": "starts_with(s, 'ab')",
     "ends_with": "ends_with(s, 'c')", "regexp_like": "regexp_like(s, '^a.*c$')",
     "regexp_replace": "regexp_replace(s, '[aeiou]', '_', 'g')", "regexp_count": "regexp_count(s, '[a-c]', 2, 'i')",      # (str, pattern[, start][, flags])
-    "chr": "chr(65)", "to_hex": "to_hex(255)",
+    "chr": "chr(65)", "to_hex": "to_hex(255)", "overlay": "overlay(s placing 'XY' from 2 for 1)",
     "levenshtein": "levenshtein(s, reverse(s))", "contains": "contains(s, 'ab')",
     "find_in_set": "find_in_set(s, 'abc,caba')", "substr_index": "substr_index(s, ' ', 2)",
     "substring_index": "substring_index(s, 'b', -1)",
