@@ -96,6 +96,10 @@ py::dict leaf_dict(const io::PqLeaf& l) {
   d["tz"] = l.tz;
   d["scale"] = l.scale;
   d["precision"] = l.precision;
+  d["top"] = l.top;
+  d["kind"] = l.kind;
+  d["rep_def"] = l.rep_def;
+  d["anc_def"] = l.anc_def;
   return d;
 }
 
@@ -142,6 +146,7 @@ kern::PqDecodeSpec decode_spec(const py::dict& d, bool need_output = true) {
   s.conv = d["conv"].cast<int>();
   s.conv_k = d["conv_k"].cast<int64_t>();
   s.max_def = d["max_def"].cast<int>();
+  s.max_rep = d.contains("max_rep") ? d["max_rep"].cast<int>() : 0;
   s.out = P<void>(d["out"].cast<uintptr_t>());
   s.valid = P<uint8_t>(d["valid"].cast<uintptr_t>());
   s.scratch = P<uint32_t>(d["scratch"].cast<uintptr_t>());
@@ -153,7 +158,7 @@ kern::PqDecodeSpec decode_spec(const py::dict& d, bool need_output = true) {
   s.raw = P<const uint8_t>(d["raw"].cast<uintptr_t>());
   s.dec = P<const uint8_t>(d["dec"].cast<uintptr_t>());
   s.error = P<int>(d["error"].cast<uintptr_t>());
-  if (s.max_def < 0 || s.max_def > 1 || s.phys < 0 || s.phys > kern::PQ_PHYS_FLBA || !s.raw || !s.error)
+  if (s.max_def < 0 || s.max_def > 3 || s.max_rep < 0 || s.max_rep > 1 || s.phys < 0 || s.phys > kern::PQ_PHYS_FLBA || !s.raw || !s.error)
     throw std::runtime_error("pq_decode: bad spec");
   if (need_output && (s.phys == kern::PQ_PHYS_BYTE_ARRAY ? !(s.codes || (s.str_len && s.str_pos)) : !s.out))
     throw std::runtime_error("pq_decode: missing output buffer");
@@ -819,18 +824,27 @@ PYBIND11_MODULE(_native, m) {
     py::gil_scoped_release rel;
     io::pread_ranges(path, rs, threads);
   });
-  m.def("pq_plan", [](uintptr_t host, const std::vector<std::tuple<int64_t, int64_t, int, int64_t, int64_t>>& chunks,
-                      int phys, int max_def, int max_rep, int64_t dec_base, int type_len) {
+  // chunks: (buffer offset, bytes, codec, first row, rows[, values]) — `values` (the footer's
+  // num_values) bounds the page walk of a repeated leaf, whose pages count entries
+  m.def("pq_plan", [](uintptr_t host, const std::vector<py::tuple>& chunks, int phys, int max_def, int max_rep,
+                      int64_t dec_base, int type_len, bool levels) {
     std::vector<io::PqChunkIn> cs;
-    for (auto& [off, len, codec, first, rows] : chunks) cs.push_back({off, len, codec, first, rows});
+    for (auto& c : chunks) {
+      if (c.size() != 5 && c.size() != 6) throw std::runtime_error("pq_plan: a chunk is 5 or 6 numbers");
+      cs.push_back({c[0].cast<int64_t>(), c[1].cast<int64_t>(), c[2].cast<int>(), c[3].cast<int64_t>(),
+                    c[4].cast<int64_t>(), c.size() == 6 ? c[5].cast<int64_t>() : -1});
+    }
     io::PqPlan plan;
     {
       py::gil_scoped_release rel;
-      plan = io::plan_column(P<const uint8_t>(host), cs, phys, max_def, max_rep, dec_base, type_len);
+      plan = io::plan_column(P<const uint8_t>(host), cs, phys, max_def, max_rep, dec_base, type_len, levels);
     }
     py::dict d;
     d["pages"] = py::bytes((const char*)plan.pages.data(), plan.pages.size());
     d["jobs"] = py::bytes((const char*)plan.jobs.data(), plan.jobs.size());
+    d["level_pages"] = py::bytes((const char*)plan.level_pages.data(), plan.level_pages.size());
+    d["num_level_pages"] = plan.num_level_pages;
+    d["num_entries"] = plan.num_entries;
     d["num_pages"] = plan.num_pages;
     d["num_jobs"] = plan.num_jobs;
     d["num_zstd_jobs"] = plan.num_zstd_jobs;
@@ -843,12 +857,13 @@ PYBIND11_MODULE(_native, m) {
     return d;
   }, "Plan GPU decode descriptors for one column's chunks staged at `host`",
      py::arg("host"), py::arg("chunks"), py::arg("phys"), py::arg("max_def"), py::arg("max_rep"),
-     py::arg("dec_base") = 0, py::arg("type_len") = 0);
+     py::arg("dec_base") = 0, py::arg("type_len") = 0, py::arg("levels") = false);
   m.def("pq_pack_spec", [](const py::dict& spec, bool need_output) {
     kern::PqDecodeSpec sp = decode_spec(spec, need_output);
     return py::bytes(reinterpret_cast<const char*>(&sp), sizeof(sp));
   }, "Validated binary PqDecodeSpec (concatenate one per column and upload)");
   m.attr("PQ_SPEC_BYTES") = (int)sizeof(kern::PqDecodeSpec);
+  m.attr("PQ_LEVEL_PAGE_BYTES") = (int)sizeof(kern::PqLevelPage);
   m.def("pq_zstd_slots", &kern::pq_zstd_slots);
   m.def("pq_zstd", [](uintptr_t jobs, int64_t njobs, uintptr_t raw, uintptr_t dec, uintptr_t lit, int64_t slots,
                       uintptr_t err, uintptr_t s) {
@@ -882,6 +897,10 @@ PYBIND11_MODULE(_native, m) {
                     P<const kern::PqDecodeSpec>(specs), S(s));
   });
   m.def("pq_str_copy", raw<&kern::pq_str_copy>);
+  m.def("pq_level_count", raw<&kern::pq_level_count>);
+  m.def("pq_list_rows", raw<&kern::pq_list_rows>);
+  m.def("pq_list_lens", raw<&kern::pq_list_lens>);
+  m.def("pq_struct_valid", raw<&kern::pq_struct_valid>);
 
   // ---------------------------------------------------------------- datagen
   // params: (kind, seed, row_base, min_len, max_len, vocab, vocab_off, vocab_n,

@@ -155,6 +155,9 @@ struct SchemaEl {
   int type = -1, type_length = 0, repetition = 0, num_children = 0, converted = -1, scale = 0, precision = 0;
   std::string name, logical;
   bool utc = false;        // TIMESTAMP logical type with isAdjustedToUTC
+  // group annotations (logical type, or converted type LIST / MAP / MAP_KEY_VALUE)
+  bool is_list() const { return logical == "list" || converted == 3; }
+  bool is_map() const { return logical == "map" || converted == 1 || converted == 2; }
   int lscale = -1, lprecision = -1;
 };
 
@@ -176,6 +179,14 @@ void parse_logical(TReader& r, SchemaEl& e) {
       case 4:   // ENUM
       case 12:  // JSON
         e.logical = "string";
+        r.skip(t);
+        break;
+      case 2:
+        e.logical = "map";
+        r.skip(t);
+        break;
+      case 3:
+        e.logical = "list";
         r.skip(t);
         break;
       case 5:
@@ -325,17 +336,19 @@ PqRowGroup parse_row_group(TReader& r) {
 }
 
 // Depth-first walk of the flattened schema tree -> leaves with def/rep levels.
-size_t flatten(const std::vector<SchemaEl>& s, size_t i, int def, int rep, const std::string& prefix,
+// rep_def: the definition level at the innermost repeated ancestor so far.
+size_t flatten(const std::vector<SchemaEl>& s, size_t i, int def, int rep, int rep_def, const std::string& prefix,
                std::vector<PqLeaf>& out) {
   const SchemaEl& e = s[i];
   const int d = def + (e.repetition != 0 ? 1 : 0);
   const int rr = rep + (e.repetition == 2 ? 1 : 0);
+  const int rd = e.repetition == 2 ? d : rep_def;
   const std::string name = prefix.empty() ? e.name : prefix + "." + e.name;
   size_t next = i + 1;
   if (e.num_children > 0) {
     for (int c = 0; c < e.num_children; ++c) {
       if (next >= s.size()) throw ParquetError("schema: truncated element list");
-      next = flatten(s, next, d, rr, name, out);
+      next = flatten(s, next, d, rr, rd, name, out);
     }
     return next;
   }
@@ -345,6 +358,7 @@ size_t flatten(const std::vector<SchemaEl>& s, size_t i, int def, int rep, const
   l.type_length = e.type_length;
   l.max_def = d;
   l.max_rep = rr;
+  l.rep_def = rd;
   l.converted_type = e.converted;
   l.logical = e.logical.empty() ? logical_from_converted(e.converted) : e.logical;
   l.tz = e.utc ? "UTC" : "";
@@ -352,6 +366,43 @@ size_t flatten(const std::vector<SchemaEl>& s, size_t i, int def, int rep, const
   l.precision = e.lprecision >= 0 ? e.lprecision : e.precision;
   out.push_back(std::move(l));
   return next;
+}
+
+bool is_leaf(const SchemaEl& e) { return e.num_children == 0; }
+
+// Shape of the top-level column at s[i] whose leaves are out[first..): the
+// kind of every leaf, from the group structure alone.
+//   LIST     group (LIST) { repeated group { T element } }     3-level, any names
+//            group (LIST) { repeated T element }               legacy 2-level
+//   MAP      group (MAP) { repeated group { required K key; V value } }
+//   STRUCT   group { flat fields }
+// Any other group (nested children, an unannotated repeated field) is "nested".
+void classify(const std::vector<SchemaEl>& s, size_t i, size_t first, std::vector<PqLeaf>& out) {
+  const SchemaEl& e = s[i];
+  auto all = [&](const char* kind) {
+    for (size_t k = first; k < out.size(); ++k) out[k].kind = kind;
+  };
+  if (is_leaf(e)) return all(e.repetition == 2 ? "nested" : "flat");
+  all("nested");
+  if (e.repetition == 2) return;
+  const SchemaEl& c = s[i + 1];   // first child (flatten() checked the element list)
+  if (e.is_list()) {
+    if (e.num_children != 1 || c.repetition != 2) return;
+    if (is_leaf(c) || (c.num_children == 1 && is_leaf(s[i + 2]) && s[i + 2].repetition != 2)) all("list");
+    return;
+  }
+  if (e.is_map()) {
+    if (e.num_children != 1 || c.repetition != 2 || c.num_children != 2) return;
+    const SchemaEl &k = s[i + 2], &v = s[i + 3];
+    if (!is_leaf(k) || !is_leaf(v) || k.repetition != 0 || v.repetition == 2) return;
+    out[first].kind = "map_key";
+    out[first + 1].kind = "map_value";
+    return;
+  }
+  if (!e.logical.empty() || e.converted >= 0) return;
+  for (int k = 0; k < e.num_children; ++k)
+    if (!is_leaf(s[i + 1 + k]) || s[i + 1 + k].repetition == 2) return;   // flat fields follow one another
+  all("struct_field");
 }
 
 int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
@@ -412,7 +463,13 @@ PqFileMeta parse_file_meta(const uint8_t* p, size_t n) {
   size_t next = 1;
   for (int c = 0; c < schema[0].num_children; ++c) {
     if (next >= schema.size()) throw ParquetError("schema: truncated element list");
-    next = flatten(schema, next, 0, 0, "", m.leaves);
+    const size_t at = next, first = m.leaves.size();
+    next = flatten(schema, at, 0, 0, 0, "", m.leaves);
+    classify(schema, at, first, m.leaves);
+    for (size_t k = first; k < m.leaves.size(); ++k) {
+      m.leaves[k].top = schema[at].name;
+      m.leaves[k].anc_def = schema[at].repetition != 0 ? 1 : 0;
+    }
   }
   for (auto& g : m.row_groups)
     if (g.chunks.size() != m.leaves.size()) throw ParquetError("footer: row group column count != schema leaves");
@@ -531,17 +588,23 @@ void pread_ranges(const std::string& path, const std::vector<ReadRange>& ranges,
 }
 
 PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, int phys, int max_def, int max_rep,
-                   int64_t dec_base, int type_len) {
+                   int64_t dec_base, int type_len, bool levels) {
   PqPlan plan;
   plan.dec_bytes = align_up(dec_base, 16);
-  if (max_rep > 0) {
-    plan.unsupported = "repeated (nested) column";
+  if (max_rep > 1) {
+    plan.unsupported = "repeated column nested more than one level deep";
     return plan;
   }
-  if (max_def > 1) {
-    plan.unsupported = "nested optional column (max definition level > 1)";
+  if (max_def > 3 || max_def < max_rep) {
+    plan.unsupported = "nested optional column (max definition level " + std::to_string(max_def) + ")";
     return plan;
   }
+  // a repeated leaf is planned in entry space: one output row per (repetition,
+  // definition) pair, positions running through every chunk of the leaf
+  const bool repeated = max_rep > 0;
+  levels = levels || repeated;
+  std::vector<kern::PqLevelPage> level_pages;
+  int64_t entry_base = 0;
   if (phys == PQ_INT96 || phys < 0 || phys > PQ_FLBA) {
     plan.unsupported = "physical type " + std::to_string(phys);
     return plan;
@@ -566,10 +629,14 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
     const bool snappy = ch.codec != PQ_UNCOMPRESSED;   // a decompression job per page (snappy or zstd)
     int64_t pos = ch.buf_off;
     const int64_t end = ch.buf_off + ch.length;
-    int64_t rows = 0;
+    int64_t rows = 0;       // output rows of the chunk so far: entries for a repeated leaf
+    int64_t v2_rows = 0;    // rows the v2 page headers claim
+    bool all_v2 = true, chunk_start = true;
+    const int64_t want = !repeated ? ch.num_rows : ch.num_values >= 0 ? ch.num_values : INT64_MAX;
     int64_t dict_off = -1;
     int32_t dict_count = 0, dict_flags = 0;
-    while (pos < end && rows < ch.num_rows) {
+    bool have_dict = false;   // an all-NULL chunk has a dictionary page with no entries
+    while (pos < end && rows < want) {
       const PqPageHeader h = parse_page_header(host + pos, (size_t)(end - pos));
       const int64_t payload = pos + h.header_len;
       if (payload + h.compressed > end) throw ParquetError("column chunk: truncated page");
@@ -584,7 +651,8 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
           plan.unsupported = "dictionary page encoding " + std::to_string(h.encoding);
           return plan;
         }
-        if (dict_count) throw ParquetError("column chunk: two dictionary pages");
+        if (have_dict) throw ParquetError("column chunk: two dictionary pages");
+        have_dict = true;
         if (snappy && h.compressed > 0) {
           dict_off = add_job(payload, h.compressed, h.uncompressed);
           dict_flags = kern::PQ_DICT_IN_DEC;
@@ -619,7 +687,7 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
         plan.unsupported = "data page encoding " + std::to_string(enc);
         return plan;
       }
-      if (dict_enc && dict_count == 0 && h.num_values > 0 && h.num_values != h.num_nulls)
+      if (dict_enc && !have_dict && h.num_values > 0 && h.num_values != h.num_nulls)
         throw ParquetError("dictionary-encoded page without a dictionary page");
       if (!dict_enc) ++plan.plain_pages;
       int64_t nrows;
@@ -628,6 +696,11 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
           plan.unsupported = "bit-packed definition levels";
           return plan;
         }
+        if (repeated && h.rep_encoding != PQ_RLE) {
+          plan.unsupported = "bit-packed repetition levels";
+          return plan;
+        }
+        all_v2 = false;
         pg.kind = kern::PQ_PAGE_DATA_V1;
         if (snappy && h.compressed > 0) {
           pg.data_off = add_job(payload, h.compressed, h.uncompressed);
@@ -638,9 +711,10 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
         pg.size = h.uncompressed;
         nrows = h.num_values;
       } else {
-        if (h.rep_len != 0) throw ParquetError("repetition levels in a flat column");
+        if (!repeated && h.rep_len != 0) throw ParquetError("repetition levels in a flat column");
+        if (h.rep_len < 0 || h.def_len < 0) throw ParquetError("v2 page: negative level length");
         pg.kind = kern::PQ_PAGE_DATA_V2;
-        pg.levels_off = payload;
+        pg.levels_off = payload + h.rep_len;   // the definition bytes follow the repetition bytes
         pg.levels_len = h.def_len;
         const int64_t vsrc = payload + h.def_len + h.rep_len;
         const int64_t vcomp = (int64_t)h.compressed - h.def_len - h.rep_len;
@@ -653,7 +727,8 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
           pg.data_off = vsrc;
         }
         pg.size = (int32_t)vunc;
-        nrows = h.num_rows ? h.num_rows : h.num_values;
+        nrows = repeated ? h.num_values : h.num_rows ? h.num_rows : h.num_values;
+        v2_rows += h.num_rows;
       }
       pg.num_values = (int32_t)nrows;
       pg.encoding = enc;
@@ -665,7 +740,27 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
         pg.aux_off = plan.dec_bytes;
         plan.dec_bytes = align_up(plan.dec_bytes + std::max<int64_t>(nrows, 1) * w, 16);
       }
-      pg.out_row = ch.first_row + rows;
+      pg.out_row = repeated ? entry_base + rows : ch.first_row + rows;
+      if (levels) {
+        kern::PqLevelPage lp{};
+        if (h.type == PQ_DATA_PAGE) {
+          lp.rep_off = pg.data_off;
+          lp.def_off = -1;
+          lp.rep_len = pg.size;
+          lp.flags = kern::PQ_LEVEL_V1 | ((pg.flags & kern::PQ_DATA_IN_DEC) ? kern::PQ_LEVEL_IN_DEC : 0);
+        } else {
+          lp.rep_off = payload;
+          lp.def_off = payload + h.rep_len;
+          lp.rep_len = h.rep_len;
+          lp.def_len = h.def_len;
+        }
+        lp.entry_base = pg.out_row;
+        lp.first_row = chunk_start ? ch.first_row : -1;
+        lp.num_entries = (int32_t)nrows;
+        if (chunk_start) lp.flags |= kern::PQ_LEVEL_CHUNK_START;
+        level_pages.push_back(lp);
+        chunk_start = false;
+      }
       pg.dict_off = dict_count ? dict_off : -1;
       pg.flags |= dict_flags;
       pg.dict_base = (int32_t)dict_base;
@@ -674,9 +769,20 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
       plan.max_page_values = std::max<int64_t>(plan.max_page_values, nrows);
       rows += nrows;
     }
-    if (rows != ch.num_rows)
+    if (repeated) {
+      // entries against the footer's value count; rows only where every page header
+      // states them (v2) — for v1 pages the row kernels compare on the device
+      if (ch.num_values >= 0 && rows != ch.num_values)
+        throw ParquetError("column chunk holds " + std::to_string(rows) + " values, the footer says " +
+                           std::to_string(ch.num_values));
+      if (all_v2 && v2_rows != ch.num_rows)
+        throw ParquetError("column chunk holds " + std::to_string(v2_rows) + " rows, row group says " +
+                           std::to_string(ch.num_rows));
+      entry_base += rows;
+    } else if (rows != ch.num_rows) {
       throw ParquetError("column chunk holds " + std::to_string(rows) + " rows, row group says " +
                          std::to_string(ch.num_rows));
+    }
     dict_base += dict_count;
     plan.dict_entries += dict_count;
     if (dict_base > INT32_MAX) {
@@ -685,6 +791,10 @@ PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, in
     }
   }
   plan.num_pages = (int64_t)pages.size();
+  plan.num_entries = entry_base;
+  plan.num_level_pages = (int64_t)level_pages.size();
+  plan.level_pages.resize(level_pages.size() * sizeof(kern::PqLevelPage));
+  if (!level_pages.empty()) std::memcpy(plan.level_pages.data(), level_pages.data(), plan.level_pages.size());
   plan.num_jobs = (int64_t)jobs.size();
   plan.pages.resize(pages.size() * sizeof(kern::PqPage));
   if (!pages.empty()) std::memcpy(plan.pages.data(), pages.data(), plan.pages.size());

@@ -49,6 +49,11 @@ struct PqLeaf {
   int scale = 0, precision = 0;
   std::string logical;     // "", "string", "decimal", "date", "timestamp_ms/us/ns", "int8/16/32/64", "uint..."
   std::string tz;          // "UTC": TIMESTAMP(isAdjustedToUTC = true), instants; "": local (naive) time
+  // the leaf's place in its top-level column, read off the group structure (never off names)
+  std::string top;         // name of the top-level column
+  std::string kind;        // "flat", "list", "map_key", "map_value", "struct_field"; "nested": any other shape
+  int rep_def = 0;         // definition level at the repeated ancestor (0: none)
+  int anc_def = 0;         // definition level from which the top-level column is non-NULL
 };
 
 struct PqChunk {
@@ -118,11 +123,15 @@ struct PqChunkIn {
   int codec;
   int64_t first_row;  // output row of the chunk's first value
   int64_t num_rows;
+  int64_t num_values = -1;  // repeated leaves: entries of the chunk (ColumnMetaData.num_values)
 };
 
 struct PqPlan {
   std::vector<uint8_t> pages;  // packed kern::PqPage
   std::vector<uint8_t> jobs;   // packed kern::PqSnappyJob
+  std::vector<uint8_t> level_pages;  // packed kern::PqLevelPage, one per data page: a repeated leaf, or `levels` asked
+  int64_t num_level_pages = 0;
+  int64_t num_entries = 0;     // (repetition, definition) pairs over all chunks = rows of the decoded leaf
   int64_t num_pages = 0, num_jobs = 0, num_dict_pages = 0;
   int64_t num_zstd_jobs = 0;   // of num_jobs
   int64_t dec_bytes = 0;     // device bytes needed for decompressed payloads
@@ -134,8 +143,9 @@ struct PqPlan {
 
 // dec_base: first free byte of the (shared) decompression buffer; plan.dec_bytes
 // is returned as the end of this column's slots (dec_base included).
+// levels: also emit the PqLevelPage table (always emitted for a repeated leaf).
 PqPlan plan_column(const uint8_t* host, const std::vector<PqChunkIn>& chunks, int phys_type, int max_def,
-                   int max_rep, int64_t dec_base = 0, int type_len = 0);
+                   int max_rep, int64_t dec_base = 0, int type_len = 0, bool levels = false);
 
 }  // namespace io
 }  // namespace igloo

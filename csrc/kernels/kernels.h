@@ -648,7 +648,7 @@ struct PqPage {
   int64_t out_row;     // first output row
   int64_t aux_off;     // DELTA_* / BYTE_STREAM_SPLIT pages: decoded values (decompression buffer); -1 otherwise
   int32_t size;        // payload bytes at data_off
-  int32_t num_values;  // rows of the page (flat columns)
+  int32_t num_values;  // rows of the page (flat columns); entries (leaves of LIST / MAP columns)
   int32_t levels_len;  // v2 definition-level bytes
   int32_t encoding;    // parquet Encoding of the values
   int32_t kind;        // PqPageKind
@@ -672,7 +672,7 @@ static_assert(sizeof(PqSnappyJob) == 32, "PqSnappyJob layout is shared with the 
 struct PqDecodeSpec {
   int32_t phys, type_len, out_width, conv;
   int64_t conv_k;   // PQ_CONV_MUL / PQ_CONV_DIV factor
-  int32_t max_def, pad;
+  int32_t max_def, max_rep;  // max_rep > 0: v1 pages carry a repetition stream before the definition stream
   void* out;        // fixed width values [rows]
   uint8_t* valid;   // [rows] or null (then the column must have no NULLs)
   uint32_t* scratch;  // [rows] compact value index -> dictionary index / byte offset
@@ -702,6 +702,39 @@ void pq_dict_strings(const PqPage* pages, int64_t npages, const int32_t* page_co
 void pq_decode(const PqPage* pages, int64_t npages, const int32_t* page_col, const PqDecodeSpec* specs,
                hipStream_t stream);
 void pq_str_copy(const int64_t* pos, const int64_t* off, int64_t n, uint8_t* out, hipStream_t stream);
+
+// ---- parquet_nested.hip (Dremel levels of LIST / MAP / STRUCT leaves -> parent rows)
+// Where one data page's level streams are (planned next to its PqPage). An
+// entry is one (repetition, definition) pair: an element, a NULL element, or
+// the placeholder of an empty / NULL list; entry positions count through
+// every page and chunk of the leaf.
+enum PqLevelFlags : int { PQ_LEVEL_V1 = 1, PQ_LEVEL_IN_DEC = 2, PQ_LEVEL_CHUNK_START = 4 };
+struct PqLevelPage {
+  int64_t rep_off;     // v2: repetition bytes (raw buffer); v1: the page payload, which starts with the
+                       // length-prefixed repetition stream (when max_rep > 0), then the definition stream
+  int64_t def_off;     // v2: definition bytes (raw buffer); v1: -1
+  int64_t entry_base;  // position of the page's first entry
+  int64_t first_row;   // PQ_LEVEL_CHUNK_START: output row of the chunk's first row; -1 otherwise
+  int32_t rep_len;     // v2: repetition bytes; v1: payload bytes
+  int32_t def_len;     // v2: definition bytes
+  int32_t num_entries;
+  int32_t flags;       // PqLevelFlags
+};
+static_assert(sizeof(PqLevelPage) == 48, "PqLevelPage layout is shared with the host planner");
+
+// Opening entries (repetition level 0) of every page -> counts[page]
+void pq_level_count(const PqLevelPage* pages, int64_t npages, const uint8_t* raw, const uint8_t* dec,
+                    int32_t* counts, int* error, hipStream_t stream);
+// row_base = exclusive scan of counts ([npages + 1]). Every opening entry e writes data[row] = (e, has
+// slots) and valid[row] (valid may be null); flags [entries] is scratch. n rows, E entries.
+void pq_list_rows(const PqLevelPage* pages, int64_t npages, const uint8_t* raw, const uint8_t* dec, int max_def,
+                  int rep_def, const int64_t* row_base, uint8_t* flags, int64_t* data, uint8_t* valid, int64_t n,
+                  int64_t E, int* error, hipStream_t stream);
+// data[row] = (start, has slots) -> (start, length)
+void pq_list_lens(int64_t* data, int64_t n, int64_t E, hipStream_t stream);
+// valid[out_row + i] = def[i] >= anc_def over the pages of one field of a STRUCT (no repetition)
+void pq_struct_valid(const PqLevelPage* pages, int64_t npages, const uint8_t* raw, const uint8_t* dec, int max_def,
+                     int anc_def, uint8_t* valid, int64_t n, int* error, hipStream_t stream);
 
 // ---- window.hip (window functions over rows sorted by partition / order keys)
 enum WinVal { kWinI64 = 0, kWinI32 = 1, kWinF64 = 2, kWinOne = 3, kWinHeadIdx = 4, kWinHead2 = 5 };

@@ -16,8 +16,9 @@ or — for a ``local`` dataset whose files already hold this rank's hash
 partition (models/tpch/parquet_gen.py) — all of them. On a GPU the column
 chunks are staged with native preads + one H2D copy and their pages are
 decompressed and decoded by gfx950 kernels (connectors/gpu_parquet.py);
-columns that decoder does not handle (nested, INT96, non-snappy codecs, DELTA
-encodings) and CPU scans use the host decoder (pyarrow). IO errors raise.
+LIST / MAP / STRUCT columns of flat values included; columns that decoder does
+not handle (deeper nesting, INT96, GZIP / LZ4 / BROTLI codecs, DELTA_BYTE_ARRAY)
+and CPU scans use the host decoder (pyarrow). IO errors raise.
 ``GPU_DECODE = False`` forces the host decoder.
 
 The source itself keeps nothing resident: the engine wraps it in the cache

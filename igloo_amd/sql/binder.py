@@ -720,6 +720,14 @@ class Binder:
             except PlanError:
                 if len(parts) == 1 and parts[0] in ("current_date", "current_timestamp", "localtimestamp"):
                     return self._func_library(parts[0].replace("localtimestamp", "current_timestamp"), [])
+                if len(parts) > 1:
+                    # s.a / t.s.a: a field of a STRUCT column (get_field) when no column has that name
+                    try:
+                        base = self.bind_expr({"k": "col", "c": node["c"][:-1]}, scope, allow_agg)
+                    except PlanError:
+                        base = None
+                    if base is not None and base.dtype.kind == "struct" and parts[-1] in dict(base.dtype.fields):
+                        return Func("get_field", [base], dict(base.dtype.fields)[parts[-1]], (parts[-1],))
                 raise
             r = ci.ref()
             if depth > 0:
