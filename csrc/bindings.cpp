@@ -454,6 +454,10 @@ PYBIND11_MODULE(_native, m) {
     auto d = agg_descs(descs);
     kern::agg_update(P<const int32_t>(gid), n, ngroups, d.data(), (int)d.size(), S(s), sorted_gids);
   }, py::arg("gid"), py::arg("n"), py::arg("ngroups"), py::arg("descs"), py::arg("s"), py::arg("sorted_gids") = false);
+  // ---- moments.hip
+  m.def("agg_moments2", raw<&kern::agg_moments2>);
+  m.attr("MOMENTS_LDS_MAX_GROUPS") = (int)kern::kMomentsLdsMaxGroups;
+  m.attr("MOMENTS_ROWS_PER_BLOCK") = (int)kern::kMomentsRowsPerBlock;
   m.def("agg_part_buckets", &kern::agg_part_buckets);
   m.def("agg_part_blocks", &kern::agg_part_blocks);
   // phase 0 / 1 / 2 of the radix-partitioned aggregate; vals: one pointer per desc (0: COUNT(*))

@@ -291,6 +291,21 @@ void agg_partitioned(const int32_t* gid, int64_t n, int64_t ngroups, const AggDe
 void agg_update(const int32_t* gid, int64_t n, int ngroups, const AggDesc* descs, int nagg, hipStream_t stream,
                 bool sorted_gids = false);
 
+// ---- moments.hip ---------------------------------------------------------------
+// the few-groups regime keeps 8 words per group (two shifts, six states) in
+// <= 64 KiB of LDS, so several workgroups stay resident per CU
+constexpr int kMomentsLdsBytes = 64 * 1024;
+constexpr int kMomentsLdsMaxGroups = kMomentsLdsBytes / (8 * 8);
+constexpr int kMomentsRowsPerBlock = 512;   // rows a workgroup takes per grid step, every regime
+// Per group over the rows with valid[i] != 0 (null: all) and gid[i] in [0, ngroups) (gid null: one
+// group): cnt[g] pairs, first[g] = the first such row (int32, or int64 with first64) and, with
+// (Kx, Ky) = (x, y)[first[g]], five sums `sum_stride` elements apart in `sums`: sum(x - Kx),
+// sum(y - Ky), sum((x - Kx)^2), sum((y - Ky)^2), sum((x - Kx)(y - Ky)). The caller zeroes cnt and
+// sums and fills first with its type's maximum (what a group without a pair keeps).
+void agg_moments2(const int32_t* gid, int64_t n, int ngroups, const double* x, const double* y, const uint8_t* valid,
+                  int64_t* cnt, void* first, bool first64, double* sums, int64_t sum_stride, bool sorted_gids,
+                  hipStream_t stream);
+
 // ---- gather.hip ----------------------------------------------------------------
 struct GatherDesc {
   const void* src;

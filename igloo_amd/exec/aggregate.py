@@ -20,6 +20,7 @@ from ..columnar import LazyColumn, Batch, Column, batch_device
 from ..ops import agg as A
 from ..ops import hashing as H
 from ..ops import misc as M
+from ..ops import moments as MO
 from ..ops import strings as S
 from ..ops._lib import (capturing, check_not_capturing, device_ints, launch, ptr, stream, to_host_f64s, to_host_int,
                        to_host_ints, unlogged)
@@ -27,7 +28,7 @@ from ..utils import tags, trace as _trace
 from ..ops.gather import gather_tensor, take, take_many
 from ..ops.select import count_true, exclusive_scan, mask_to_indices
 from ..sql import logical as L
-from ..sql.expr import AggCall, BinOp, ColRef, Expr, Lit, and_all, col_refs, conjuncts
+from ..sql.expr import REGR_FUNCS, AggCall, BinOp, ColRef, Expr, Lit, and_all, col_refs, conjuncts
 from ..utils.errors import ExecutionError, NotSupported
 from . import fused
 from .expr_eval import Evaluator, Scalar, _convert_tensor
@@ -615,10 +616,11 @@ def aggregate(groups, aggs, b: Batch, ctx, row_parts: Optional[Dict[int, int]] =
             idx = b.parts[k][1]
             out[cid] = Column(T.INT64, gather_tensor(idx, rep).to(torch.int64))
     specs, finals = [], []
+    shared: dict = {}        # states several aggregates of this call read (the regr_* moments)
     with ctx.span("agg.eval_args"):
         ev.prefetch([a.arg for _, a in aggs] + [getattr(a, "arg2", None) for _, a in aggs], b)
         for ci, a in aggs:
-            _plan_agg(ci, a, b, gid, ng, n, ctx, specs, finals)
+            _plan_agg(ci, a, b, gid, ng, n, ctx, specs, finals, shared)
     with ctx.span("agg.kernel"):
         results = A.grouped_aggregate(gid, ng, [s[:3] for s in specs], n, dev,
                                       sorted_gids=gid is not None and getattr(ctx, "sorted_gids", False)) \
@@ -815,8 +817,31 @@ def _empty_col(t, dev) -> Column:
     return Column(t, torch.zeros(0, dtype=t.torch_dtype if t.kind != "null" else torch.bool, device=dev))
 
 
-def _plan_agg(ci, a: AggCall, b: Batch, gid, ng, n, ctx, specs, finals):
-    """Append kernel specs for one aggregate and a finaliser producing its column."""
+def _regr(func: str, cnt, mx, my, m2x, m2y, cxy) -> Column:
+    """One regr_* column from a group's pair count, means and centred sums."""
+    if func == "regr_count":
+        return Column(T.INT64, cnt)
+    some = cnt > 0
+    if func in ("regr_avgx", "regr_avgy", "regr_sxx", "regr_syy", "regr_sxy"):
+        v = {"regr_avgx": mx, "regr_avgy": my, "regr_sxx": m2x, "regr_syy": m2y, "regr_sxy": cxy}[func]
+        return Column(T.FLOAT64, v, some)
+    # NULL for fewer than two pairs or a constant x (M2x = 0; a NaN M2x is not 0: it propagates)
+    ok = (cnt > 1) & (m2x != 0)
+    den = torch.where(ok, m2x, torch.ones_like(m2x))
+    slope = cxy / den
+    if func == "regr_slope":
+        return Column(T.FLOAT64, slope, ok)
+    if func == "regr_intercept":
+        return Column(T.FLOAT64, my - slope * mx, ok)
+    flat = m2y == 0           # a constant y is fitted exactly
+    r2 = torch.where(flat, torch.ones_like(cxy), cxy * cxy / (den * torch.where(flat, torch.ones_like(m2y), m2y)))
+    return Column(T.FLOAT64, r2, ok)
+
+
+def _plan_agg(ci, a: AggCall, b: Batch, gid, ng, n, ctx, specs, finals, shared: Optional[dict] = None):
+    """Append kernel specs for one aggregate and a finaliser producing its
+    column. ``shared``: per-Aggregate states that several of its aggregates
+    read, so they are computed once."""
     ev = ctx.evaluator
     dev = ctx.device
     func = a.func
@@ -871,6 +896,21 @@ def _plan_agg(ci, a: AggCall, b: Batch, gid, ng, n, ctx, specs, finals):
     if func == "string_agg":
         out = _string_agg(a, col, valid, gid, ng, n, ctx, b)
         finals.append(lambda r, out=out: (ci, out))
+        return
+    if func in REGR_FUNCS:
+        # regr_*(y, x): every call over the same (y, x, FILTER) of this Aggregate
+        # reads one grouped_moments2 result (one pass over x and y)
+        key = ("moments2", a.arg.sql(), a.arg2.sql(), a.filter.sql() if a.filter is not None else None)
+        mom = None if shared is None else shared.get(key)
+        if mom is None:
+            cx = ev.column(a.arg2, b)
+            both = valid if cx.valid is None else (cx.valid if valid is None else valid & cx.valid)
+            mom = MO.grouped_moments2(gid, ng, _convert_tensor(cx, T.FLOAT64).contiguous(),
+                                      _convert_tensor(col, T.FLOAT64).contiguous(), both, n, dev,
+                                      sorted_gids=gid is not None and getattr(ctx, "sorted_gids", False))
+            if shared is not None:
+                shared[key] = mom
+        finals.append(lambda r, mom=mom: (ci, _regr(func, *mom)))
         return
     if func in ("covar_samp", "covar_pop", "corr"):
         c2 = ev.column(a.arg2, b)

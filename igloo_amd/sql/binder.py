@@ -19,8 +19,8 @@ from .. import types as T
 from . import template as TPL
 from ..types import BOOL, DATE32, FLOAT64, INT32, INT64, UTF8, DataType
 from ..utils.errors import ExecutionError, NotSupported, PlanError, TableNotFound
-from .expr import (AGG_FUNCS, FRAME_KINDS, RANKING_FUNCS, VALUE_FUNCS, AggCall, BinOp, Case, Cast, ColRef, Expr,
-                   Func, InList, IsNull, Like, Lit, Neg, Not, SubqueryExpr, WindowCall, WindowFrame, and_all, col_refs,
+from .expr import (AGG_FUNCS, FRAME_KINDS, RANKING_FUNCS, REGR_FUNCS, VALUE_FUNCS, AggCall, BinOp, Case, Cast, ColRef,
+                   Expr, Func, InList, IsNull, Like, Lit, Neg, Not, SubqueryExpr, WindowCall, WindowFrame, and_all, col_refs,
                    transform, walk)
 from .logical import (Aggregate, ColInfo, Filter, Join, Limit, Plan, Project, RecursiveCTE, Scan, Sort, Union, Values,
                       TableFunction, Unnest, Window, WorkTableScan)
@@ -1180,9 +1180,11 @@ class Binder:
                 if not args:
                     raise PlanError(f"{name}() needs an argument")
                 arg = args[0]
-                if name in ("covar", "covar_samp", "covar_pop", "corr"):
+                if name in ("covar", "covar_samp", "covar_pop", "corr") or name in REGR_FUNCS:
                     if len(args) != 2:
                         raise PlanError(f"{name}() takes two arguments")
+                    if distinct and name in REGR_FUNCS:
+                        raise PlanError(f"{name}(DISTINCT ..) is not valid")
                     arg2 = args[1]
                 elif name in ("percentile_cont", "percentile_disc"):
                     # percentile_cont(x, q): the DataFusion function-call spelling
@@ -2209,6 +2211,7 @@ _EXTRA_AGGS = ("stddev_samp", "stddev_pop", "var_samp", "var_pop", "variance", "
                "median", "approx_distinct", "approx_median", "string_agg", "array_agg", "bit_and", "bit_or",
                "bit_xor", "percentile_cont", "percentile_disc", "covar", "covar_samp", "covar_pop", "corr", "approx_percentile_cont", "first_value",
                "last_value", "every", "any", "some")
+_EXTRA_AGGS += REGR_FUNCS
 
 
 _TRUNC_UNITS = ("microsecond", "millisecond", "second", "minute", "hour", "day", "week", "month", "quarter", "year")
@@ -2534,6 +2537,11 @@ def _make_agg(name: str, arg: Optional[Expr], distinct: bool, flt, arg2: Optiona
         if not (t.is_numeric and arg2 is not None and arg2.dtype.is_numeric):
             raise PlanError(f"{name}() needs two numeric arguments")
         return AggCall(name, arg, False, FLOAT64, flt, arg2)
+    if name in REGR_FUNCS:
+        # numeric arguments of any width (both are read as doubles)
+        if not (t.is_numeric and arg2 is not None and arg2.dtype.is_numeric):
+            raise PlanError(f"{name}() needs two numeric arguments")
+        return AggCall(name, arg, False, INT64 if name == "regr_count" else FLOAT64, flt, arg2)
     if name == "array_agg":
         return AggCall("array_agg", arg, distinct, T.LIST(t), flt, None, None, order)
     raise NotSupported(f"aggregate {name}")

@@ -258,6 +258,10 @@ class Func(Expr):
 
 AGG_FUNCS = {"sum", "count", "avg", "min", "max", "mean", "stddev", "var", "bool_and", "bool_or", "first_value",
              "array_agg", "count_distinct"}
+#: regr_*(y, x) (Postgres / DataFusion): linear regression of the first argument
+#: (dependent) on the second (independent) over the pairs with neither side NULL
+REGR_FUNCS = ("regr_count", "regr_avgx", "regr_avgy", "regr_sxx", "regr_syy", "regr_sxy", "regr_slope",
+              "regr_intercept", "regr_r2")
 
 
 @dataclass(eq=False)

@@ -66,6 +66,10 @@ AGGREGATE: Dict[str, str] = {
     "var_samp": "var_samp(f)", "var_pop": "var_pop(f)", "covar": "covar(f, n)", "covar_samp": "covar_samp(f, n)",
     "covar_pop": "covar_pop(f, n)", "corr": "corr(f, n)", "bool_and": "bool_and(n > 0)",
     "bool_or": "bool_or(n > 2)", "every": "every(n > 0)", "string_agg": "string_agg(s, ',')",
+    # regr_*(y, x): regression of y on x (ops/moments.py)
+    "regr_count": "regr_count(f, n)", "regr_avgx": "regr_avgx(f, n)", "regr_avgy": "regr_avgy(f, n)",
+    "regr_sxx": "regr_sxx(f, n)", "regr_syy": "regr_syy(f, n)", "regr_sxy": "regr_sxy(f, n)",
+    "regr_slope": "regr_slope(f, n)", "regr_intercept": "regr_intercept(f, n)", "regr_r2": "regr_r2(f, n)",
 }
 WINDOW: Dict[str, str] = {
     "row_number": "row_number() over (order by n nulls last, s nulls last)", "rank": "rank() over (order by n nulls last)",
