@@ -591,6 +591,7 @@ PYBIND11_MODULE(_native, m) {
     kern::strfmt_write(reinterpret_cast<const uint8_t*>(fmt.data()), (int)fmt.size(), is_date, P<const void>(v),
                        P<const int32_t>(offs), n, P<const int64_t>(off), out_cap, P<uint8_t>(out), S(s));
   });
+  m.def("strptime", raw<&kern::strptime>);
   m.def("tz_to_local", raw<&kern::tz_to_local>);
   m.def("tz_to_utc", raw<&kern::tz_to_utc>);
   m.def("tz_trunc", raw<&kern::tz_trunc>);

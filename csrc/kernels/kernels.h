@@ -465,6 +465,14 @@ void strfmt_lengths(const uint8_t* fmt, int flen, bool is_date, const void* v, c
 void strfmt_write(const uint8_t* fmt, int flen, bool is_date, const void* v, const int32_t* offs, int64_t n,
                   const int64_t* off, int64_t out_cap, uint8_t* out, hipStream_t s);
 
+// ---- strptime.hip (to_timestamp / to_date with a list of chrono-style formats) ---
+// prog: plen bytes of compiled formats in HOST memory (ops/strptime.py compile_formats; at most 256, copied
+// into the kernel arguments). unit: 0 us, 1 ms, 2 s (int64 microseconds floored to the unit), 3 day (int32
+// day numbers). chars holds nbytes bytes; a row outside them fails. err[0] starts at n and receives the
+// smallest non-NULL row that no format matched (such a row's value is 0).
+void strptime(const uint8_t* prog, int plen, int unit, const int64_t* off, const uint8_t* chars, int64_t nbytes,
+              const uint8_t* valid, int64_t n, void* out, int64_t* err, hipStream_t s);
+
 // ---- tz.hip (TIMESTAMP WITH TIME ZONE: conversions through a compiled zone table) ---
 // tab: one device buffer [trans P int64][wall P int64][offs P int32], P = 1 << log2p (utils/tzdb.py);
 // log2p < 0: a fixed-offset zone (fixed_off seconds, tab unused). utc_lo / wall_lo: where the 400-year

@@ -527,6 +527,9 @@ class Evaluator:
             if isinstance(c, Scalar):
                 c = Column.full(c.value, e.args[0].dtype, b.num_rows, self.device(b))
             return DG.hex_digest(c, e.options[0]) if name == "hex_digest" else DG.to_char(c, e.options[0])
+        if name == "strptime":
+            from ..ops import strptime as SP
+            return SP.strptime(args[0], *e.options)
         if name in ("bin_encode", "bin_decode", "byte_length"):
             from ..ops import binary as BN
             c = args[0]
@@ -633,6 +636,9 @@ class Evaluator:
         if name == "to_unixtime":
             c = args[0]
             return Column(T.INT64, torch.div(c.data.to(torch.int64), 1_000_000, rounding_mode="floor"), c.valid)
+        if name == "ts_from_nanos":
+            c = args[0]
+            return Column(T.TIMESTAMP, torch.div(c.data.to(torch.int64), 1000, rounding_mode="floor"), c.valid)
         if name == "ts_from_float":
             c = args[0]
             return Column(T.TIMESTAMP, (c.data.to(torch.float64) * 1e6).round().to(torch.int64), c.valid)
@@ -837,6 +843,11 @@ class Evaluator:
                 return Scalar(SR.py_row(name[:-4])(strs, ints), T.UTF8)
             except ValueError as ex:
                 raise ExecutionError(str(ex)) from None
+        if name == "strptime":
+            from ..ops import strptime as SP
+            return Scalar(SP.fold(_text(vals[0]), *e.options), e.dtype)
+        if name == "ts_from_nanos":
+            return Scalar(int(vals[0]) // 1000, e.dtype)
         if name == "upper":
             return Scalar(vals[0].upper(), T.UTF8)
         if name == "lower":

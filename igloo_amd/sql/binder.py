@@ -1279,6 +1279,8 @@ class Binder:
         if name in ("power", "pow"):
             return Func("power", [self._coerce(a, FLOAT64) for a in args], FLOAT64)
         if name in ("to_date",):
+            if len(args) > 1:
+                return self._strptime(name, args)
             return self._coerce(args[0], DATE32)
         if name == "arrow_typeof":
             _nargs(name, args, 1)
@@ -1987,12 +1989,20 @@ class Binder:
                 origin = int(o.value)
             return Func("date_bin", [x], x.dtype, (stride, origin))
         if name in ("to_timestamp", "to_timestamp_micros", "to_timestamp_millis", "to_timestamp_seconds",
-                    "from_unixtime"):
+                    "to_timestamp_nanos", "from_unixtime"):
+            if len(args) > 1 and name != "from_unixtime":
+                return self._strptime(name, args)
             x = args[0]
             if x.dtype.is_string:
                 if isinstance(x, Lit):
                     return _fold_cast(x, T.TIMESTAMP)
                 return Cast(x, T.TIMESTAMP)
+            if name == "to_timestamp_nanos":
+                # the engine's timestamp is microseconds: nanoseconds floor toward -inf
+                x = self._coerce(x, INT64)
+                if isinstance(x, Lit):
+                    return TPL.derive(lambda a: Lit(None if a.value is None else int(a.value) // 1000, T.TIMESTAMP), x)
+                return Func("ts_from_nanos", [x], T.TIMESTAMP)
             scale = {"to_timestamp_micros": 1, "to_timestamp_millis": 1000}.get(name, 1_000_000)
             if name == "to_timestamp" and x.dtype.is_float:
                 return Func("ts_from_float", [x], T.TIMESTAMP)
@@ -2036,6 +2046,29 @@ class Binder:
                 return Lit(None if x.value is None else x.value * 86_400_000_000, T.TIMESTAMP)
             return Cast(x, T.TIMESTAMP)
         return self._coerce(x, T.TIMESTAMP)
+
+    def _strptime(self, name: str, args: List[Expr]) -> Expr:
+        """to_timestamp*(s, f1 [, f2 ...]) / to_date(s, f1 [, ...]): text read by the first chrono format
+        that matches it (ops/strptime.py). The formats live in the Func's options, so a statement
+        template is keyed on them; an all-literal call folds through the Python twin."""
+        from ..ops import strptime as SP
+        unit = "date" if name == "to_date" else name[len("to_timestamp_"):] or "timestamp"
+        t = DATE32 if unit == "date" else T.TIMESTAMP
+        formats = []
+        for a in args[1:]:
+            if not isinstance(a, Lit) or not isinstance(a.value, str):      # (.value keys a template on the format)
+                raise NotSupported(f"{name}(): the formats must be string constants")
+            formats.append(a.value)
+        formats = tuple(formats)
+        x = args[0]
+        if x.dtype.kind == "null":
+            return Lit(None, t)
+        if not x.dtype.is_string:
+            raise NotSupported(f"{name}(value, format, ...): the value must be text, got {x.dtype}")
+        SP.compile_formats(formats)         # a format outside the grammar is a PlanError here
+        if isinstance(x, Lit):
+            return TPL.derive(lambda a, f=formats, u=unit, t=t: Lit(SP.fold(a.value, f, u), t), x)
+        return Func("strptime", [x], t, (formats, unit))
 
     def _arith_ts_scale(self, x: Expr, scale: int) -> Expr:
         if isinstance(x, Lit):

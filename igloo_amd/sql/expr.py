@@ -252,6 +252,12 @@ class Func(Expr):
     def sql(self):
         if self.name == "try_cast":
             return f"TRY_CAST({self.args[0].sql()} AS {self.dtype})"
+        if self.name == "strptime":
+            # as it was written: to_timestamp_millis(s, '%d/%m/%Y', '%F')
+            formats, unit = self.options
+            fn = "to_date" if unit == "date" else "to_timestamp" if unit == "timestamp" else f"to_timestamp_{unit}"
+            quoted = ", ".join("'" + f.replace("'", "''") + "'" for f in formats)
+            return f"{fn}({self.args[0].sql()}, {quoted})"
         opt = f"[{','.join(map(str, self.options))}]" if self.options else ""
         return f"{self.name}{opt}({', '.join(a.sql() for a in self.args)})"
 

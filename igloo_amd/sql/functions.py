@@ -50,6 +50,7 @@ DATETIME: Dict[str, str] = {
     "current_timestamp": "current_timestamp > ts", "current_date": "current_date > d", "today": "today() > d",
     "to_timestamp": "to_timestamp(n)", "to_timestamp_seconds": "to_timestamp_seconds(n)",
     "to_timestamp_millis": "to_timestamp_millis(n)", "to_timestamp_micros": "to_timestamp_micros(n)",
+    "to_timestamp_nanos": "to_timestamp_nanos(n)",
     "from_unixtime": "from_unixtime(n)", "to_unixtime": "to_unixtime(ts)", "to_date": "to_date('2024-01-02')",
     "make_date": "make_date(2020, n, 1)", "date_bin": "date_bin(interval '15 minutes', ts)",
     "to_local_time": "to_local_time(ts at time zone '+02:00')",

@@ -554,7 +554,7 @@ def perturb(texts: List[str], kinds: List[str], nodes: List[dict]) -> List[str]:
                 d = datetime.date.fromisoformat(t.strip()) + datetime.timedelta(days=1)
                 out.append(d.isoformat())
                 continue
-            except ValueError:
+            except (ValueError, OverflowError):      # (no day after 9999-12-31)
                 out.append(t)
                 continue
         if k == "str":
