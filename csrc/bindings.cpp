@@ -788,6 +788,11 @@ PYBIND11_MODULE(_native, m) {
   m.def("win_frame_minmax", raw<&kern::win_frame_minmax>);
   m.def("win_rank", raw<&kern::win_rank>);
   m.def("win_index", raw<&kern::win_index>);
+  m.def("win_frame_kth", raw<&kern::win_frame_kth>);
+  m.def("win_select_tile", &kern::win_select_tile);
+  m.def("win_select_levels", &kern::win_select_levels);
+  m.def("win_select_build", raw<&kern::win_select_build>);
+  m.def("win_select_query", raw<&kern::win_select_query>);
 
   // ---------------------------------------------------------------- parquet
   m.def("pq_file_meta", [](const std::string& path) {

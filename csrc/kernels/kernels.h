@@ -790,6 +790,21 @@ void win_rank(int fn, int64_t arg, int64_t n, const int64_t* seg_start, const in
 void win_index(int fn, int64_t arg, int64_t n, const int64_t* seg_start, const int64_t* seg_end, const int64_t* lo,
                const int64_t* hi, int64_t* out, hipStream_t s);
 
+// ---- window_select.hip (order statistics over window frames; routines in window_select.h)
+// Rows of ranks k0 / k1 (k1, pos1: nullptr = one rank) among the valid values of each row's frame [lo, hi];
+// -1: malformed frame or rank outside [0, count). vals: int64 (floats as f64_ord images).
+// win_frame_kth: a loop over the frame, for frames of a few rows.
+void win_frame_kth(const int64_t* vals, const uint8_t* valid, int64_t n, const int64_t* lo, const int64_t* hi,
+                   const int64_t* k0, const int64_t* k1, int64_t* pos0, int64_t* pos1, hipStream_t s);
+// The merge-sort tree: perm = the m (2 <= m < 2^31) valid positions by ascending (value, position);
+// tree = levels = win_select_levels(m) = ceil(log2 m) runs of m int32.
+int win_select_tile();
+int win_select_levels(int64_t m);
+void win_select_build(const int32_t* perm, int64_t m, int levels, int32_t* tree, hipStream_t s);
+void win_select_query(const int32_t* perm, const int32_t* tree, int levels, int64_t m, int64_t n, const int64_t* lo,
+                      const int64_t* hi, const int64_t* k0, const int64_t* k1, int64_t* pos0, int64_t* pos1,
+                      hipStream_t s);
+
 // ---- strfunc.hip (scalar string functions over plain UTF-8 columns)
 enum StrFnCode {
   kSfTrim = 0, kSfReplace = 1, kSfLpad = 2, kSfRpad = 3, kSfReverse = 4, kSfRepeat = 5, kSfLeft = 6, kSfRight = 7,

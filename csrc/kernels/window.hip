@@ -21,6 +21,10 @@
 //     frames) or a sparse table (win_sparse_*), both in the f64_ord order.
 //   * win_rank / win_index: ranking functions and the source row of
 //     lag / lead / first_value / last_value / nth_value.
+// Framed order statistics (median / percentile_* OVER a frame) are neither a
+// prefix difference nor a two-block lookup: their selection kernels are in
+// window_select.hip (a counting loop for narrow frames, a merge-sort tree over
+// value ranks for wide ones).
 // Parity: DataFusion's WindowAggExec / BoundedWindowAggExec, reached by the
 // reference through SessionContext::sql (reference crates/engine/src/lib.rs:54-57,
 // Cargo.lock datafusion-functions-window 48.0.0).

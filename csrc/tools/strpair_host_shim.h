@@ -2,7 +2,8 @@
 // strpair.hip / strfunc.hip as plain C++ (one "thread" after another) under ASan / UBSan.
 // tests/test_strpair_host.py copies it next to copies of the two kernel files as common.h;
 // csrc/tools/textparse_host.cpp (tests/test_textparse_host.py) uses it the same way for textparse.h,
-// csrc/tools/binary_host.cpp (tests/test_binary_host.py) for binary.hip and digest.hip.
+// csrc/tools/binary_host.cpp (tests/test_binary_host.py) for binary.hip and digest.hip,
+// csrc/tools/winselect_host.cpp (tests/test_winselect_host.py) for window_select.h.
 #pragma once
 #include <cstdint>
 #include <cstdlib>

@@ -22,6 +22,11 @@ segmented scan or an elementwise pass over the sorted order
   if and only if some output row's exact sum lies outside int64: the scans
   flag exactly that for running ROWS frames, and the other frames sum
   32-bit halves;
+* median / percentile_cont / percentile_disc (and the approx_* spellings)
+  over any frame: the frame's valid count gives the wanted ranks, the rows
+  holding them come from ``frame_kth`` (a counting loop for narrow frames,
+  a merge-sort tree over value ranks for wide ones: window_select.hip) and
+  the arithmetic of the GROUP BY form runs on the values gathered there;
 * lag / lead / first_value / last_value / nth_value: a source-row index
   per row and one gather.
 
@@ -474,6 +479,51 @@ def _aggregate(w: WindowCall, b: Batch, st: _Sorted, lo, hi, ctx) -> Column:
         var = ((s2 - c * mean * mean) / (c if pop else (c - 1)).clamp(min=1)).clamp(min=0)
         out = var.sqrt() if f.startswith("stddev") else var
         return Column(T.FLOAT64, out, c > (0 if pop else 1))
+    if f in ("median", "percentile", "percentile_disc"):
+        # order statistics: the rows holding the wanted ranks of every frame
+        # (ops/window.py frame_kth), then the arithmetic of aggregate._order_stat
+        # on the values gathered there. [lo, hi] serves every frame shape.
+        t = w.dtype
+        fl = src.is_float or col.is_wide or f == "percentile"
+        # a 64-bit decimal under percentile_cont is ranked on its unscaled integers (the same order) and
+        # only the picked values become doubles, by a true division: a tensor divisor, since the device
+        # turns a division by a host scalar into a multiplication by its reciprocal, one ulp off the host's
+        unscale = None
+        if f == "percentile" and src.is_decimal and not col.is_wide:
+            fl = False
+            unscale = torch.full((), float(10**src.scale), dtype=torch.float64, device=dev)
+        x = (_convert_tensor(col, T.FLOAT64) if fl else col.data.to(torch.int64)).contiguous()
+        c = W.frame_sum(None, prefix(None, W.V_ONE, W.SUM_I), lo, hi, n)[1]
+        ok = c > 0
+        last = (c - 1).clamp(min=0)
+        if f == "percentile_disc":
+            k0 = (torch.ceil(c.to(torch.float64) * float(w.options[0])).to(torch.int64) - 1).clamp(min=0)
+            k1 = None
+        elif f == "percentile":
+            pos = last.to(torch.float64) * float(w.options[0])
+            k0 = pos.floor().to(torch.int64)
+            frac = pos - k0.to(torch.float64)
+            k1 = torch.minimum(k0 + 1, last)
+        else:
+            k0 = torch.div(c - 1, 2, rounding_mode="floor")
+            k1 = torch.div(c, 2, rounding_mode="floor")
+        p0, p1 = W.frame_kth(x, valid, lo, hi, k0, k1, n)
+        v0 = gather_tensor(x, p0.clamp(min=0))
+        if f == "percentile_disc":
+            return Column(t, v0 if t.is_decimal else v0.to(t.torch_dtype), ok)
+        v1 = gather_tensor(x, p1.clamp(min=0))
+        if f == "percentile":
+            if unscale is not None:
+                v0, v1 = v0.to(torch.float64) / unscale, v1.to(torch.float64) / unscale
+            return Column(T.FLOAT64, v0 + (v1 - v0) * frac, ok)
+        if x.dtype == torch.float64:
+            med = (v0 + v1) / 2
+            return Column(t, med if t.is_float else med.to(torch.int64), ok)
+        # trunc((v0 + v1) / 2) without forming the sum, which may leave int64:
+        # the floor of the mean, plus one where the sum is odd and negative
+        med = (v0 >> 1) + (v1 >> 1) + (v0 & v1 & 1)
+        med = med + ((med < 0) & (((v0 ^ v1) & 1) != 0)).to(torch.int64)
+        return Column(t, med.to(t.torch_dtype) if not t.is_decimal else med, ok)
     raise NotSupported(f"window aggregate {f}")
 
 

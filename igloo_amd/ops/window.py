@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import is_gpu, launch, ptr, stream, to_host_int
+from ._lib import is_gpu, launch, ptr, stream, to_host_int, to_host_ints
 
 # value sources (kernels.h WinVal)
 V_I64, V_I32, V_F64, V_ONE, V_HEADIDX, V_HEAD2 = range(6)
@@ -359,6 +359,97 @@ def frame_minmax(vals: torch.Tensor, valid: Optional[torch.Tensor], lo, hi, n: i
     if f64:
         out = torch.where(ok, _f64_ord(out), out).view(torch.float64)
     return out, ok
+
+
+#: positions one workgroup sorts inside LDS when the merge-sort tree is built
+#: (window_select.h kSelectTile): sizes around it cross from one tile to several
+SELECT_TILE = 2048
+
+
+def frame_kth(vals: torch.Tensor, valid: Optional[torch.Tensor], lo, hi, k0, k1, n: int):
+    """Order statistics of each row's frame: the positions (rows of the
+    window-sorted order) holding ranks ``k0`` and ``k1`` (None: one rank; then
+    the second result is None) among the valid values of frame [lo, hi], in
+    (value, position) order. -1 where the rank is outside [0, count), the frame
+    is empty or it does not lie inside [0, n). ``vals``: int64, or float64,
+    which compares as its ``_f64_ord`` image (NaN above +inf, -0.0 below +0.0).
+
+    GPU: frames of at most LOOP_MAX_WIDTH rows take a counting loop
+    (``win_frame_kth``); wider ones a merge-sort tree over value ranks
+    (``win_select``: one argsort, ceil(log2 m) levels of m int32 for m valid
+    rows, freed on return, and a descent of about log2(m)^2 loads per row).
+    CPU: a numpy sort of every frame's valid (value, position) pairs, O(n w)
+    pairs for frames of w rows: the oracle of the GPU paths, sharing no code
+    with them."""
+    from ..utils.errors import NotSupported
+    if n >= 2**31:
+        raise NotSupported("order statistics over window frames of 2^31 or more rows")
+    dev = lo.device
+    if n == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        return z, (z.clone() if k1 is not None else None)
+    v = vals.contiguous()
+    v = _f64_ord(v.to(torch.float64).view(torch.int64)) if v.dtype.is_floating_point else v.to(torch.int64)
+    if not lo.is_cuda:
+        return _frame_kth_cpu(v, valid, lo, hi, k0, k1, n)
+    lo, hi, k0 = lo.contiguous(), hi.contiguous(), k0.contiguous()
+    k1 = k1.contiguous() if k1 is not None else None
+    valid = valid.contiguous() if valid is not None else None
+    pos0 = torch.empty(n, dtype=torch.int64, device=dev)
+    pos1 = torch.empty(n, dtype=torch.int64, device=dev) if k1 is not None else None
+    width = (hi - lo).max() + 1
+    if valid is None:
+        widest, m = to_host_int(width), n
+    else:
+        widest, m = to_host_ints(torch.stack([width, valid.sum()]))
+    if widest <= LOOP_MAX_WIDTH:
+        launch("win_frame_kth").win_frame_kth(ptr(v), ptr(valid), n, ptr(lo), ptr(hi), ptr(k0), ptr(k1), ptr(pos0),
+                                              ptr(pos1), stream(pos0))
+        return pos0, pos1
+    from . import sort as SO
+    if m <= 1:
+        # no tree to build: nothing is valid, or one row is
+        if m == 0:
+            pos0.fill_(-1)
+            return pos0, (pos1.fill_(-1) if pos1 is not None else None)
+        p = valid.to(torch.int64).argmax()
+        inside = (lo >= 0) & (hi < n) & (lo <= p) & (p <= hi)
+        neg = torch.full_like(lo, -1)
+        return torch.where(inside & (k0 == 0), p, neg), \
+            (torch.where(inside & (k1 == 0), p, neg) if k1 is not None else None)
+    perm = SO.argsort([(v, False, False, valid)], n, dev)
+    ranks = perm[:m].to(torch.int32).contiguous()       # level 0: the valid positions by ascending value
+    N = launch("win_select")
+    assert N.win_select_tile() == SELECT_TILE
+    levels = (m - 1).bit_length()
+    tree = torch.empty((levels, m), dtype=torch.int32, device=dev)
+    st = stream(pos0)
+    N.win_select_build(ptr(ranks), m, levels, ptr(tree), st)
+    N.win_select_query(ptr(ranks), ptr(tree), levels, m, n, ptr(lo), ptr(hi), ptr(k0), ptr(k1), ptr(pos0), ptr(pos1),
+                       st)
+    del tree
+    return pos0, pos1
+
+
+def _frame_kth_cpu(v, valid, lo, hi, k0, k1, n):
+    import numpy as np
+    x = v.numpy()
+    ok = valid.numpy().astype(bool) if valid is not None else None
+    lo_, hi_ = lo.numpy(), hi.numpy()
+    ks = [k0.numpy()] + ([k1.numpy()] if k1 is not None else [])
+    out = [np.full(n, -1, dtype=np.int64) for _ in ks]
+    for r in range(n):
+        a, b = int(lo_[r]), int(hi_[r])
+        if a < 0 or b >= n or b < a:
+            continue
+        idx = np.arange(a, b + 1)
+        if ok is not None:
+            idx = idx[ok[a:b + 1]]
+        order = idx[np.argsort(x[idx], kind="stable")]      # (value, position): positions ascend inside a tie
+        for k, o in zip(ks, out):
+            if 0 <= k[r] < order.size:
+                o[r] = order[k[r]]
+    return torch.from_numpy(out[0]), (torch.from_numpy(out[1]) if k1 is not None else None)
 
 
 def rank(fn: int, arg: int, n: int, ss, se, ps, pe, dense, device) -> torch.Tensor:

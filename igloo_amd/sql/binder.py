@@ -2153,16 +2153,37 @@ class Binder:
                 raise PlanError(f"{name}() takes one argument")
             return WindowCall(name, [x], part, order, frame, x.dtype)
         if name in AGG_FUNCS or name in _EXTRA_AGGS:
+            if node.get("within_group") is not None:
+                raise NotSupported(f"{name}() WITHIN GROUP as a window function")
+            param = None
+            if name in ("percentile_cont", "percentile_disc", "approx_percentile_cont") and len(args) == 2:
+                # the fraction: a literal, carried in the call's options (the errors of the GROUP BY form);
+                # reading .value keys a statement template on it
+                q = args[1]
+                if not isinstance(q, Lit) or q.value is None:
+                    raise PlanError(f"{name}() takes a constant fraction" if name != "approx_percentile_cont" else
+                                    f"{name}() takes a constant second argument")
+                if isinstance(q.value, (str, bytes, bool)):
+                    raise PlanError(f"{name}() takes a constant fraction")
+                param = float(q.value) / (10 ** q.dtype.scale if q.dtype.is_decimal else 1)
+                if not 0.0 <= param <= 1.0:
+                    raise PlanError("percentile must be between 0 and 1")
+                args = args[:1]
             if node.get("star") or not args:
                 arg = None
             elif len(args) == 1:
                 arg = args[0]
             else:
                 raise NotSupported(f"window aggregate {name} with {len(args)} arguments")
-            a = _make_agg(name, arg, False, None)
+            a = _make_agg(name, arg, False, None, None, param)
             if a.func not in _WINDOW_AGGS:
                 raise NotSupported(f"{name}() as a window function")
-            return WindowCall(a.func, [arg] if arg is not None else [], part, order, frame, a.dtype, flt)
+            opts = ()
+            if a.func in ("percentile", "percentile_disc"):
+                if param is None:
+                    raise PlanError(f"{name}() takes a constant fraction")
+                opts = (param,)
+            return WindowCall(a.func, [arg] if arg is not None else [], part, order, frame, a.dtype, flt, opts)
         raise NotSupported(f"window function {name}()")
 
     def _window_spec(self, w: dict) -> dict:
@@ -2239,7 +2260,7 @@ class _Passthrough(ColRef):
 # ---------------------------------------------------------------------- helpers
 #: aggregates computed by the window operator (exec/window.py)
 _WINDOW_AGGS = ("sum", "count", "avg", "min", "max", "stddev", "stddev_samp", "stddev_pop", "var", "var_samp",
-                "var_pop", "bool_and", "bool_or")
+                "var_pop", "bool_and", "bool_or", "median", "percentile", "percentile_disc")
 _EXTRA_AGGS = ("stddev_samp", "stddev_pop", "var_samp", "var_pop", "variance", "var_population", "stddev_population",
                "median", "approx_distinct", "approx_median", "string_agg", "array_agg", "bit_and", "bit_or",
                "bit_xor", "percentile_cont", "percentile_disc", "covar", "covar_samp", "covar_pop", "corr", "approx_percentile_cont", "first_value",

@@ -342,9 +342,11 @@ class WindowFrame:
 @dataclass(eq=False)
 class WindowCall(Expr):
     """``func(args) [FILTER (WHERE f)] OVER (PARTITION BY .. ORDER BY .. frame)``.
-    Aggregates (sum/count/avg/min/max/stddev/var/bool_*), ranking functions
-    and value functions; ``options`` holds constant arguments (ntile buckets,
-    lag/lead offset, nth_value position)."""
+    Aggregates (sum/count/avg/min/max/stddev/var/bool_* and the order
+    statistics median / percentile / percentile_disc, under the function names
+    of ``AggCall``), ranking functions and value functions; ``options`` holds
+    constant arguments (ntile buckets, lag/lead offset, nth_value position,
+    the fraction q of percentile / percentile_disc as a float in [0, 1])."""
     func: str
     args: List[Expr]
     partition: List[Expr]
